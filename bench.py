@@ -19,6 +19,13 @@ cache-hit profile comparable to (slightly harder than) the real graph.
 
 Weak scaling: each rank trains batches of 1024 from its own seed stream.
 value = whole-job sampled-edges/sec through the FULL training step.
+
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the
+N steps and prints one JSON result line.  `--dump-outputs DIR` also writes
+outputs of that same run as .npy files (inputs and parameter init are
+seeded, so two runs and two builds can be compared output for output; see
+DUMP_EARLY_STEP for which step's model output is written); `--full` is
+where secondary measurements go.
 """
 import argparse
 import json
@@ -55,6 +62,56 @@ FANOUT = [15, 10, 5]
 HIDDEN = 256
 
 REF_EPOCH_SECONDS = {1: 11.1, 2: 5.8, 3: 4.7, 4: 3.25}  # products only
+
+# --dump-outputs: total bytes written stay under 64 MB (.npy headers
+# included)
+DUMP_BUDGET_BYTES = 60_000_000
+# --dump-outputs writes the sampler's and the feature store's outputs of
+# the LAST timed step (n_id, x, edge indices: bit-identical from run to
+# run), but the model's output and loss of an EARLY step: step 1 of the
+# run counting from 0, warmup included — parameters after exactly one
+# optimizer update, so it reflects one full backward.  The backward
+# kernels scatter with float atomics whose summation order differs every
+# run, and Adam amplifies that rounding noise ~1.7x per step; measured
+# run-to-run max |diff| of the [1024, 47] log-probabilities (|values| <=
+# 6) on one MI355X, fp32: 0 after 1 step, 9.5e-7 after 5, 4.9e-2 after 25,
+# 1.3e-1 after 55.  The last step's model output therefore says nothing
+# about a build that its own noise does not drown.  At step 1 the spread
+# is rounding: <= 9.5e-7 (2 ulp) in fp32, 1 bf16 ulp (3.1e-2) with
+# --dtype bf16, whatever --steps and --warmup are.
+DUMP_EARLY_STEP = 1
+
+
+def dump_outputs(out_dir, arrays):
+    """Write the given output tensors as out_dir/<name>.npy.
+
+    arrays: list of (name, tensor, axis).  Floating tensors are stored as
+    float32, integer tensors (node ids, edge indices — all far below 2^53)
+    as float64, so two builds can be compared array for array with plain
+    numpy.  When everything together would exceed DUMP_BUDGET_BYTES, each
+    large array keeps a fixed sample along `axis`: ascending indices drawn
+    with a constant seed that depend only on the array's extent, so equal
+    outputs give equal files."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = []
+    for name, t, axis in arrays:
+        t = t.detach()
+        t = t.to(torch.float32 if t.is_floating_point() else torch.float64)
+        host.append((name, t.cpu().numpy(), axis))
+    # smallest first: an array that fits its equal share of what is left
+    # is written whole and leaves the rest of its share to the larger ones
+    left = DUMP_BUDGET_BYTES
+    host.sort(key=lambda e: e[1].nbytes)
+    for i, (name, a, axis) in enumerate(host):
+        share = left // (len(host) - i)
+        if a.nbytes > share:
+            extent = a.shape[axis]
+            keep = max(1, share // (a.nbytes // extent))
+            pick = np.sort(np.random.default_rng(0).choice(
+                extent, size=keep, replace=False))
+            a = np.take(a, pick, axis=axis)
+        left -= a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def make_graph(seed=0, nodes=None, edges=None, max_deg=20_000):
@@ -129,7 +186,19 @@ def main():
                         "feature-store bytes (incl. the PCIe cold tier) "
                         "and is reported as its own honestly-labeled "
                         "variant")
+    p.add_argument("--full", action="store_true",
+                   help="also run secondary measurements; there are none "
+                        "yet, so this equals a plain run")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last timed "
+                        "step's frontier node ids, gathered features and "
+                        "per-layer edge indices, and the model output and "
+                        "loss of step 1 of the run (see DUMP_EARLY_STEP), "
+                        "as DIR/<name>.npy, float32/float64, under 64 MB "
+                        "in all; rank 0 only")
     args = p.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        p.error("--dump-outputs needs at least one timed step")
 
     ps = PRESETS[args.preset]
     if args.nodes is None:
@@ -235,6 +304,9 @@ def main():
         args.cache_policy = "device_replicate"
         feature = build_feature(args.cache_policy)
 
+    # seeded parameter init: with the same arguments every run starts from
+    # identical inputs, so --dump-outputs of two builds can be compared
+    torch.manual_seed(0)
     if args.model == "gat":
         model = GAT(feat_dim, HIDDEN // 4, n_classes,
                     num_layers=len(FANOUT), heads=4, dropout=0.0).to(device)
@@ -264,12 +336,22 @@ def main():
         print(f"# setup done in {time.perf_counter()-t0:.1f}s "
               f"(edges={m/1e6:.1f}M)", flush=True)
 
+    # --dump-outputs: references to the most recent step's sampler/feature
+    # tensors and to the early step's model output (no copies, no syncs
+    # inside the timed region)
+    last = {"seen": 0} if args.dump_outputs else None
+
     def train_on(n_id, bs, adjs, x):
         out = model(x, adjs)
         loss = F.nll_loss(out, y[n_id[:bs]])
         opt.zero_grad(set_to_none=True)
         loss.backward()
         opt.step()
+        if last is not None:
+            last.update(n_id=n_id, adjs=adjs, x=x)
+            if last["seen"] <= DUMP_EARLY_STEP:
+                last.update(out=out, loss=loss)
+            last["seen"] += 1
         return sum(adj.edge_index.shape[1] for adj in adjs)
 
     step_times = [] if os.environ.get("QUIVER_BENCH_STEP_TIMES") else None
@@ -329,6 +411,14 @@ def main():
     if step_times is not None and rank == 0:
         print("# step ms:", " ".join(f"{t:.2f}" for t in step_times),
               flush=True)
+    if last is not None and rank == 0:
+        arrays = [("n_id", last["n_id"], 0), ("x", last["x"], 0),
+                  ("out_early", last["out"], 0),
+                  ("loss_early", last["loss"].reshape(1), 0)]
+        # adjs[0] is the outermost hop (PyG order), as the model consumes it
+        arrays += [(f"edge_index_{i}", adj.edge_index, 1)
+                   for i, adj in enumerate(last["adjs"])]
+        dump_outputs(args.dump_outputs, arrays)
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1000
         steps_per_epoch = (n_train + args.batch * world - 1) // (args.batch *

@@ -97,9 +97,15 @@ def test_partition_info_dispatch_cpu():
     assert total == ids.numel()
 
 
-def test_topo_single_clique_without_gpu():
-    """GPU-less Topo: all-true access matrix -> one clique, stable ids."""
+def test_topo_single_clique_without_gpu(monkeypatch):
+    """GPU-less Topo: all-true access matrix -> one clique, stable ids.
+
+    The GPU-less path is forced, so the test checks the same thing on a
+    box that has fewer than four devices (where probing peers 1-3 is an
+    invalid-ordinal error) as on one that has none."""
+    import torch
     from quiver.utils import Topo
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
     t = Topo([0, 1, 2, 3])
     assert t.p2p_clique_count == 1
     assert t.cliques == [[0, 1, 2, 3]]
