@@ -10,6 +10,11 @@
 //  - rows are copied with the widest aligned vector type (16B dwordx4 when
 //    row_bytes % 16 == 0) by a subgroup of lanes sized to the row, so a
 //    wave64 moves up to 1 KiB per instruction; reference copies byte-wise.
+//  - the optional feature_order translation (id -> row) is folded into
+//    the kernel as one dependent load, so no translated index buffer is
+//    written or re-read per batch.
+//    (Alternatives measured for the pinned-host tier:
+//    profiles/GATHER_COLD_ROWS.md.)
 #include <cstdlib>
 
 #include "qk_common.h"
@@ -26,7 +31,8 @@ template <typename VecT, int SUB, bool SCATTER>
 __global__ void __launch_bounds__(BLOCK)
 copy_rows_kernel(GatherSpec spec, const int64_t* __restrict__ indices,
                  int64_t n, char* __restrict__ other,
-                 const int64_t* __restrict__ n_dev) {
+                 const int64_t* __restrict__ n_dev,
+                 const int64_t* __restrict__ order, int64_t order_n) {
     if (n_dev) n = min(n, *n_dev);
     const int sub_id = threadIdx.x / SUB;
     const int lane = threadIdx.x % SUB;
@@ -36,7 +42,12 @@ copy_rows_kernel(GatherSpec spec, const int64_t* __restrict__ indices,
     const int64_t nvec = spec.row_bytes / (int64_t)sizeof(VecT);
 
     for (; row < n; row += stride) {
-        const int64_t idx = indices[row];
+        int64_t idx = indices[row];
+        if (order) {  // feature_order fold: one dependent load
+            if (idx < 0 || idx >= order_n) continue;
+            idx = order[idx];
+        }
+        if (idx < 0) continue;
         // shard search: spec lives in kernel args (scalar regs), <=16 entries
         int s = 0;
         while (s < spec.nshards && idx >= spec.ends[s]) ++s;
@@ -95,7 +106,8 @@ inline int gather_max_blocks(const GatherSpec& spec, bool overlapped) {
 template <typename VecT, bool SCATTER>
 void dispatch_sub(hipStream_t s, const GatherSpec& spec,
                   const int64_t* indices, int64_t n, char* other,
-                  const int64_t* n_dev) {
+                  const int64_t* n_dev, const int64_t* order,
+                  int64_t order_n) {
     int64_t nvec = spec.row_bytes / (int64_t)sizeof(VecT);
     int sub = 4;
     while (sub < 64 && sub < nvec) sub *= 2;  // cover the row in ~1 pass
@@ -105,8 +117,8 @@ void dispatch_sub(hipStream_t s, const GatherSpec& spec,
     switch (sub) {
 #define QK_CASE(S)                                                          \
     case S:                                                                 \
-        copy_rows_kernel<VecT, S, SCATTER>                                  \
-            <<<grid, BLOCK, 0, s>>>(spec, indices, n, other, n_dev);        \
+        copy_rows_kernel<VecT, S, SCATTER><<<grid, BLOCK, 0, s>>>(          \
+            spec, indices, n, other, n_dev, order, order_n);                \
         break;
         QK_CASE(4) QK_CASE(8) QK_CASE(16) QK_CASE(32) QK_CASE(64)
 #undef QK_CASE
@@ -116,29 +128,36 @@ void dispatch_sub(hipStream_t s, const GatherSpec& spec,
 
 template <bool SCATTER>
 void copy_rows(hipStream_t s, const GatherSpec& spec, const int64_t* indices,
-               int64_t n, char* other, const int64_t* n_dev) {
+               int64_t n, char* other, const int64_t* n_dev,
+               const int64_t* order, int64_t order_n) {
     if (n == 0 || spec.nshards == 0) return;
     if (spec.row_bytes % 16 == 0)
-        dispatch_sub<vec16, SCATTER>(s, spec, indices, n, other, n_dev);
+        dispatch_sub<vec16, SCATTER>(s, spec, indices, n, other, n_dev,
+                                     order, order_n);
     else if (spec.row_bytes % 8 == 0)
-        dispatch_sub<uint64_t, SCATTER>(s, spec, indices, n, other, n_dev);
+        dispatch_sub<uint64_t, SCATTER>(s, spec, indices, n, other, n_dev,
+                                        order, order_n);
     else if (spec.row_bytes % 4 == 0)
-        dispatch_sub<uint32_t, SCATTER>(s, spec, indices, n, other, n_dev);
+        dispatch_sub<uint32_t, SCATTER>(s, spec, indices, n, other, n_dev,
+                                        order, order_n);
     else
-        dispatch_sub<uint8_t, SCATTER>(s, spec, indices, n, other, n_dev);
+        dispatch_sub<uint8_t, SCATTER>(s, spec, indices, n, other, n_dev,
+                                       order, order_n);
 }
 
 }  // namespace
 
 void launch_gather(hipStream_t s, const GatherSpec& spec,
                    const int64_t* indices, int64_t n, char* out,
-                   const int64_t* n_dev) {
-    copy_rows<false>(s, spec, indices, n, out, n_dev);
+                   const int64_t* n_dev, const int64_t* order,
+                   int64_t order_n) {
+    copy_rows<false>(s, spec, indices, n, out, n_dev, order, order_n);
 }
 
 void launch_scatter(hipStream_t s, const GatherSpec& spec,
                     const int64_t* indices, int64_t n, const char* src) {
-    copy_rows<true>(s, spec, indices, n, const_cast<char*>(src), nullptr);
+    copy_rows<true>(s, spec, indices, n, const_cast<char*>(src), nullptr,
+                    nullptr, 0);
 }
 
 }  // namespace qk

@@ -782,28 +782,36 @@ class ShardTensor {
         return out;
     }
 
-    torch::Tensor gather(torch::Tensor indices) {
-        return gather_on(device_, indices);
+    // order (optional, int64 on the executing device): feature_order
+    // translation folded into the gather kernels — row = order[indices[i]].
+    torch::Tensor gather(torch::Tensor indices,
+                         c10::optional<torch::Tensor> order) {
+        return gather_impl(device_, indices, torch::Tensor(),
+                           order.value_or(torch::Tensor()));
     }
 
     // Run the gather with `dev` as the executing GPU (used by the
     // cross-clique fallback: remote device reads its own HBM, result is
     // copied back by the python layer).
     torch::Tensor gather_on(int dev, torch::Tensor indices) {
-        return gather_impl(dev, indices, torch::Tensor());
+        return gather_impl(dev, indices, torch::Tensor(), torch::Tensor());
     }
 
     // n_dev: 1-element int64 CUDA tensor holding the exact row count
     // (indices is upper-bound sized); enables fully async chains.
-    torch::Tensor gather_n(torch::Tensor indices, torch::Tensor n_dev) {
-        return gather_impl(device_, indices, n_dev);
+    torch::Tensor gather_n(torch::Tensor indices, torch::Tensor n_dev,
+                           c10::optional<torch::Tensor> order) {
+        return gather_impl(device_, indices, n_dev,
+                           order.value_or(torch::Tensor()));
     }
 
     torch::Tensor gather_impl(int dev, torch::Tensor indices,
-                              torch::Tensor n_dev_t) {
+                              torch::Tensor n_dev_t, torch::Tensor order_t) {
         DeviceScope g(dev);
         indices = indices.contiguous();
         TORCH_CHECK(indices.device().is_cuda(), "indices must be on GPU");
+        TORCH_CHECK(indices.scalar_type() == torch::kInt64,
+                    "indices must be int64");
         int64_t n = indices.numel();
         std::vector<int64_t> shape = {n};
         shape.insert(shape.end(), row_shape_.begin(), row_shape_.end());
@@ -815,6 +823,17 @@ class ShardTensor {
         const int64_t* n_dev = n_dev_t.defined()
                                    ? n_dev_t.data_ptr<int64_t>()
                                    : nullptr;
+        const int64_t* order = nullptr;
+        int64_t order_n = 0;
+        if (order_t.defined()) {
+            TORCH_CHECK(order_t.is_cuda() && order_t.get_device() == dev &&
+                            order_t.scalar_type() == torch::kInt64 &&
+                            order_t.is_contiguous(),
+                        "order must be a contiguous int64 tensor on the "
+                        "executing device");
+            order = order_t.data_ptr<int64_t>();
+            order_n = order_t.numel();
+        }
 
         // Tier-split: a mixed gather would run at the capped host grid for
         // ALL rows (the cap keeps the PCIe-latency-bound zero-copy pass
@@ -835,6 +854,7 @@ class ShardTensor {
             // into pinned staging, ONE large H2D burst, then an
             // HBM-to-HBM scatter places them.  Large DMA bursts run at
             // full PCIe write bandwidth.
+            if (order) indices = order_t.index_select(0, indices);
             qk::GatherSpec ds = spec;
             ds.access_mask = dev_mask;
             ds.has_host_shard = false;
@@ -849,7 +869,26 @@ class ShardTensor {
             qk::GatherSpec ds = spec;
             ds.access_mask = dev_mask;
             ds.has_host_shard = false;
-            auto side = c10::hip::getStreamFromPool(false, dev);
+            // One side stream per executing device, taken from the pool
+            // once: the pool creates its streams lazily, so asking it per
+            // call costs a ~1.2 ms hipStreamCreateWithPriority on each of
+            // the first 32 gathers of a process.  A capturing call still
+            // takes a fresh pool stream, so a capture that fails midway
+            // can never leave the cached stream in capture state.
+            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+            (void)hipStreamIsCapturing(cur.stream(), &cs);
+            auto side = c10::hip::getCurrentHIPStream(dev);
+            if (cs != hipStreamCaptureStatusNone) {
+                side = c10::hip::getStreamFromPool(false, dev);
+            } else {
+                auto side_it = side_streams_.find(dev);
+                if (side_it == side_streams_.end())
+                    side_it = side_streams_
+                                  .emplace(dev, c10::hip::getStreamFromPool(
+                                                    false, dev))
+                                  .first;
+                side = side_it->second;
+            }
             auto& ev = split_events_[dev];  // events live on `dev`
             if (!ev.first) {
                 QK_CHECK_HIP(hipEventCreateWithFlags(
@@ -860,9 +899,11 @@ class ShardTensor {
             QK_CHECK_HIP(hipEventRecord(ev.first, cur.stream()));
             QK_CHECK_HIP(hipStreamWaitEvent(side.stream(), ev.first, 0));
             qk::launch_gather(cur.stream(), hs, indices.data_ptr<int64_t>(),
-                              n, (char*)out.data_ptr(), n_dev);
+                              n, (char*)out.data_ptr(), n_dev, order,
+                              order_n);
             qk::launch_gather(side.stream(), ds, indices.data_ptr<int64_t>(),
-                              n, (char*)out.data_ptr(), n_dev);
+                              n, (char*)out.data_ptr(), n_dev, order,
+                              order_n);
             QK_CHECK_HIP(hipEventRecord(ev.second, side.stream()));
             QK_CHECK_HIP(hipStreamWaitEvent(cur.stream(), ev.second, 0));
             // caching-allocator hazard: out/indices are used on `side`.
@@ -870,18 +911,19 @@ class ShardTensor {
             // go to the HIP allocator directly.)  Under hipGraph capture
             // the tensors live in the graph pool with static lifetime —
             // skip the bookkeeping (recordStream during capture throws).
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            (void)hipStreamIsCapturing(cur.stream(), &cs);
             if (cs == hipStreamCaptureStatusNone) {
                 c10::hip::HIPCachingAllocator::recordStream(
                     out.storage().data_ptr(), side);
                 c10::hip::HIPCachingAllocator::recordStream(
                     indices.storage().data_ptr(), side);
+                if (order)
+                    c10::hip::HIPCachingAllocator::recordStream(
+                        order_t.storage().data_ptr(), side);
             }
         } else {
             qk::launch_gather(cur.stream(), spec,
                               indices.data_ptr<int64_t>(), n,
-                              (char*)out.data_ptr(), n_dev);
+                              (char*)out.data_ptr(), n_dev, order, order_n);
         }
         return out;
     }
@@ -1114,6 +1156,7 @@ class ShardTensor {
     // (events must live on the device whose streams record them)
     mutable std::unordered_map<int, std::pair<hipEvent_t, hipEvent_t>>
         split_events_;
+    mutable std::unordered_map<int, c10::hip::HIPStream> side_streams_;
     // pinned buffers for the CPU-staged host-tier gather
     torch::Tensor idx_pin_, pos_pin_, stage_pin_;
 };
@@ -1595,13 +1638,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("append_from", &ShardTensor::append_from,
              "alias a shard owned by another same-process ShardTensor")
         .def("share_ipc", &ShardTensor::share_ipc)
-        .def("__getitem__", &ShardTensor::gather,
+        .def("__getitem__",
+             [](ShardTensor& self, torch::Tensor indices) {
+                 return self.gather(indices, c10::nullopt);
+             },
              py::call_guard<py::gil_scoped_release>())
-        .def("gather", &ShardTensor::gather,
+        .def("gather", &ShardTensor::gather, py::arg("indices"),
+             py::arg("order") = py::none(),
              py::call_guard<py::gil_scoped_release>())
         .def("gather_on", &ShardTensor::gather_on,
              py::call_guard<py::gil_scoped_release>())
-        .def("gather_n", &ShardTensor::gather_n,
+        .def("gather_n", &ShardTensor::gather_n, py::arg("indices"),
+             py::arg("n_dev"), py::arg("order") = py::none(),
              py::call_guard<py::gil_scoped_release>())
         .def("access_mask_on", &ShardTensor::access_mask_on)
         .def("shard_ends", &ShardTensor::shard_ends)

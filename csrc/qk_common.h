@@ -129,9 +129,12 @@ struct GatherSpec {
 // accessible are left untouched (python layer fills them via a peer pass).
 // n is a host upper bound; when n_dev != nullptr the exact row count is
 // read from the device (async sample+gather chains, no host sync).
+// order != nullptr folds the feature_order translation into the kernel:
+// row = order[indices[i]], indices outside [0, order_n) are skipped.
 void launch_gather(hipStream_t s, const GatherSpec& spec,
                    const int64_t* indices, int64_t n, char* out,
-                   const int64_t* n_dev = nullptr);
+                   const int64_t* n_dev = nullptr,
+                   const int64_t* order = nullptr, int64_t order_n = 0);
 
 // Scatter-style update used by the python layer for cache fill / tests:
 // shard-resident rows only.  dst row indices[i] <- src[i].

@@ -331,23 +331,28 @@ class Feature(object):
         count is read by the kernel from the 1-element device tensor
         `n_dev` — no host synchronization anywhere on the path.  Slack
         output rows are untouched; the caller slices.  Not available for
-        the disk (mmap) tier or partially-accessible shard layouts."""
+        the disk (mmap) tier or partially-accessible shard layouts.
+
+        The `feature_order` translation is not a separate indexing pass:
+        the table goes to the native gather, whose kernels look each id
+        up as one dependent load (no translated int64 temporary the size
+        of the upper-bound frontier per batch).  Cold (pinned-host) rows
+        run on the current stream at a capped grid, hot rows at full
+        grid on one cached side stream."""
         self.lazy_init_from_ipc_handle()
         if self.mmap_handle_ is not None:
             raise RuntimeError("gather_raw does not support the disk tier")
         node_idx = node_idx.to(self.rank)
-        if self.feature_order is not None:
-            node_idx = self.feature_order[node_idx]
-        return self._shard_tensor().gather_n(node_idx, n_dev)
+        return self._shard_tensor().gather_n(node_idx, n_dev,
+                                             self.feature_order)
 
     def __getitem__(self, node_idx: torch.Tensor):
         self.lazy_init_from_ipc_handle()
         node_idx = node_idx.to(self.rank)
         if self.mmap_handle_ is None:
             with trace_scope("feature.gather"):
-                if self.feature_order is not None:
-                    node_idx = self.feature_order[node_idx]
-                return self._shard_tensor()[node_idx]
+                return self._shard_tensor().gather(node_idx,
+                                                   self.feature_order)
         # disk tier: disk_map < 0 -> mmap row, >= 0 -> in-memory row
         num_nodes = node_idx.size(0)
         disk_index = self.disk_map[node_idx]

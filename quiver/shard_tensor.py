@@ -96,19 +96,28 @@ class ShardTensor:
         result = self.shard_tensor.gather_on(inter_device, request_nodes)
         wait_results.append((part_orders, result.to(self.current_device)))
 
-    def gather_n(self, nodes, n_dev):
+    def gather_n(self, nodes, n_dev, order=None):
         """Upper-bound gather with device-side exact count (async path);
-        requires every shard to be directly accessible from this device."""
+        requires every shard to be directly accessible from this device.
+        order: optional int64 id -> row table applied inside the kernels."""
         if self._inaccessible_ranges():
             raise RuntimeError("gather_n: some shards need the cross-clique "
                                "pass; use __getitem__")
         nodes = nodes.to(self.current_device)
-        return self.shard_tensor.gather_n(nodes, n_dev)
+        return self.shard_tensor.gather_n(nodes, n_dev, order)
 
     def __getitem__(self, nodes):
+        return self.gather(nodes)
+
+    def gather(self, nodes, order=None):
+        """Rows nodes (order is None) or order[nodes]; the translation runs
+        inside the gather kernels unless the peer pass needs the row ids."""
         nodes = nodes.to(self.current_device)
-        feature = self.shard_tensor[nodes]
         missing = self._inaccessible_ranges()
+        if missing and order is not None:
+            nodes = order[nodes]
+            order = None
+        feature = self.shard_tensor.gather(nodes, order)
         if missing:
             input_orders = torch.arange(nodes.size(0), dtype=torch.long,
                                         device=nodes.device)
