@@ -354,8 +354,13 @@ class GpuSampler {
     // read the sizes only when the whole chain has been consumed.
     // Frontier slack is zeroed so downstream indexing (feature_order
     // remap, gather) stays in-range.
+    // Third element: per hop, the exclusive scan of the per-dst sampled
+    // counts, one slot longer than the dst upper bound.  Slack dsts
+    // count 0, so entries [0 .. n_dst] are the hop's finished segment
+    // pointer (dst_ptr[n_dst] == m_h) — consumers narrow it to n_dst + 1
+    // instead of rebuilding it with a searchsorted over the edge list.
     std::tuple<std::vector<std::tuple<torch::Tensor, torch::Tensor>>,
-               torch::Tensor>
+               torch::Tensor, std::vector<torch::Tensor>>
     sample_hops_raw(torch::Tensor seeds, const std::vector<int>& ks) {
         DeviceScope g(device_);
         auto stream = current_stream();
@@ -376,22 +381,27 @@ class GpuSampler {
         torch::Tensor cur = seeds;
         const int64_t* n_dev = nullptr;     // exact frontier count (device)
         int64_t n_ub = seeds.numel();       // upper bound (host)
-        std::vector<torch::Tensor> frontiers, hop_edges;
+        std::vector<torch::Tensor> frontiers, hop_edges, dst_ptrs;
         std::vector<int64_t> n_ubs;
 
         for (int h = 0; h < H; ++h) {
             const int k = ks[h];
             const int64_t m_ub = n_ub * k;
-            auto counts = torch::empty({n_ub}, opts);
+            // counts/prefix carry one extra slot past the n_ub dsts: a
+            // zero count (written by the count kernel itself; `cur` has no
+            // element n_ub to read), so the scan leaves prefix[n_ub] ==
+            // m_h and prefix doubles as the hop's dst segment pointer
+            auto counts = torch::empty({n_ub + 1}, opts);
             qk::launch_capped_degree(stream, indptr_.data_ptr<int64_t>(),
                                      cur.data_ptr<int64_t>(), n_ub, k,
-                                     counts.data_ptr<int64_t>(), n_dev);
-            auto prefix = torch::empty({n_ub}, opts);
-            auto temp = torch::empty({(int64_t)qk::scan_temp_bytes(n_ub)},
+                                     counts.data_ptr<int64_t>(), n_dev,
+                                     /*zero_extra_slot=*/true);
+            auto prefix = torch::empty({n_ub + 1}, opts);
+            auto temp = torch::empty({(int64_t)qk::scan_temp_bytes(n_ub + 1)},
                                      opts.dtype(torch::kUInt8));
             qk::launch_exclusive_scan(stream, temp.data_ptr(), temp.numel(),
                                       counts.data_ptr<int64_t>(),
-                                      prefix.data_ptr<int64_t>(), n_ub,
+                                      prefix.data_ptr<int64_t>(), n_ub + 1,
                                       sd + 2 * h);  // m_h
             auto out = torch::empty({m_ub}, opts);
             const uint64_t salt = (uint64_t)(h + 1) * 0xD1B54A32D192ED03ULL;
@@ -452,6 +462,7 @@ class GpuSampler {
 
             frontiers.push_back(frontier);
             hop_edges.push_back(edges);
+            dst_ptrs.push_back(prefix);
             n_ubs.push_back(n_ub);
             cur = frontier;
             n_dev = sd + 2 * h + 1;
@@ -461,21 +472,34 @@ class GpuSampler {
         std::vector<std::tuple<torch::Tensor, torch::Tensor>> raw;
         for (int h = 0; h < H; ++h)
             raw.emplace_back(frontiers[h], hop_edges[h]);
-        return {raw, sizes_dev};
+        return {raw, sizes_dev, dst_ptrs};
+    }
+
+    // Exact-sized per hop (frontier, edge_index, dst_ptr[n_dst + 1]).
+    std::vector<std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>>
+    sample_hops_ptr(torch::Tensor seeds, const std::vector<int>& ks) {
+        auto [raw, sizes_dev, dst_ptrs] = sample_hops_raw(seeds, ks);
+        // the ONE sync of the whole batch
+        auto sizes_host = sizes_dev.cpu();
+        const int64_t* sh = sizes_host.data_ptr<int64_t>();
+        std::vector<std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>>
+            res;
+        int64_t n_dst = seeds.numel();
+        for (size_t h = 0; h < raw.size(); ++h) {
+            int64_t m = sh[2 * h], u = sh[2 * h + 1];
+            res.emplace_back(std::get<0>(raw[h]).narrow(0, 0, u),
+                             std::get<1>(raw[h]).narrow(1, 0, m),
+                             dst_ptrs[h].narrow(0, 0, n_dst + 1));
+            n_dst = u;
+        }
+        return res;
     }
 
     std::vector<std::tuple<torch::Tensor, torch::Tensor>>
     sample_hops(torch::Tensor seeds, const std::vector<int>& ks) {
-        auto [raw, sizes_dev] = sample_hops_raw(seeds, ks);
-        // the ONE sync of the whole batch
-        auto sizes_host = sizes_dev.cpu();
-        const int64_t* sh = sizes_host.data_ptr<int64_t>();
         std::vector<std::tuple<torch::Tensor, torch::Tensor>> res;
-        for (size_t h = 0; h < raw.size(); ++h) {
-            int64_t m = sh[2 * h], u = sh[2 * h + 1];
-            res.emplace_back(std::get<0>(raw[h]).narrow(0, 0, u),
-                             std::get<1>(raw[h]).narrow(1, 0, m));
-        }
+        for (auto& [frontier, edges, ptr] : sample_hops_ptr(seeds, ks))
+            res.emplace_back(frontier, edges);
         return res;
     }
 
@@ -1189,15 +1213,41 @@ torch::Tensor segment_mean_gather(torch::Tensor x, torch::Tensor src,
     return out;
 }
 
-torch::Tensor segment_mean_gather_backward(torch::Tensor grad_out,
-                                           torch::Tensor src,
-                                           torch::Tensor dst_ptr,
-                                           int64_t n_src) {
+// grad_x [n_src, D] = scatter of grad_out over the edges, on top of
+// `grad_self` in the leading rows (or zeros when grad_self is absent).
+static torch::Tensor segment_mean_backward_onto(
+    torch::Tensor grad_out, const c10::optional<torch::Tensor>& grad_self,
+    torch::Tensor src, torch::Tensor dst_ptr, int64_t n_src) {
+    TORCH_CHECK(grad_out.is_cuda() && grad_out.dim() == 2 &&
+                (grad_out.dtype() == torch::kFloat32 ||
+                 grad_out.dtype() == torch::kBFloat16));
     grad_out = grad_out.contiguous();
     src = src.contiguous();
     dst_ptr = dst_ptr.contiguous();
     int64_t n_dst = dst_ptr.numel() - 1;
-    auto grad_x = torch::zeros({n_src, grad_out.size(1)}, grad_out.options());
+    const int64_t dim = grad_out.size(1);
+    TORCH_CHECK(grad_out.size(0) == n_dst,
+                "segment mean backward: grad_out rows != dst_ptr segments");
+    auto grad_x = torch::empty({n_src, dim}, grad_out.options());
+    const int64_t row_bytes = dim * (int64_t)grad_out.element_size();
+    const void* head = nullptr;
+    int64_t head_bytes = 0;
+    torch::Tensor gs;
+    if (grad_self.has_value() && grad_self->defined()) {
+        gs = grad_self->contiguous();
+        TORCH_CHECK(gs.dim() == 2 && gs.size(1) == dim &&
+                    gs.size(0) <= n_src && gs.dtype() == grad_out.dtype() &&
+                    gs.device() == grad_out.device(),
+                    "segment mean backward: self-path gradient must be "
+                    "[<= n_src, D] of grad_out's dtype and device");
+        head = gs.data_ptr();
+        head_bytes = gs.size(0) * row_bytes;
+    }
+    if (grad_out.dtype() == torch::kBFloat16)
+        TORCH_CHECK(dim % 2 == 0,
+                    "bf16 segment mean needs an even feature dim");
+    qk::launch_prefix_fill(current_stream(), head, head_bytes,
+                           n_src * row_bytes, grad_x.data_ptr());
     if (grad_out.dtype() == torch::kBFloat16) {
         TORCH_CHECK(grad_out.size(1) % 2 == 0,
                     "bf16 segment mean needs an even feature dim");
@@ -1213,6 +1263,25 @@ torch::Tensor segment_mean_gather_backward(torch::Tensor grad_out,
                                 dst_ptr.data_ptr<int64_t>(), n_dst,
                                 grad_out.size(1), grad_x.data_ptr<float>());
     return grad_x;
+}
+
+torch::Tensor segment_mean_gather_backward(torch::Tensor grad_out,
+                                           torch::Tensor src,
+                                           torch::Tensor dst_ptr,
+                                           int64_t n_src) {
+    return segment_mean_backward_onto(grad_out, c10::nullopt, src, dst_ptr,
+                                      n_src);
+}
+
+// Whole input gradient of a layer that uses x both as the aggregation
+// source and as x[:n_self] (bipartite prefix convention): one fill pass
+// (self-path gradient rows, zeros below) plus the scatter, instead of
+// zeros + scatter + zero-padded slice gradient + add.
+torch::Tensor segment_mean_prefix_backward(
+    torch::Tensor grad_agg, c10::optional<torch::Tensor> grad_self,
+    torch::Tensor src, torch::Tensor dst_ptr, int64_t n_src) {
+    return segment_mean_backward_onto(grad_agg, grad_self, src, dst_ptr,
+                                      n_src);
 }
 
 // Tall-skinny weight gradient: (A^T @ B, optional column-sums of A).
@@ -1592,6 +1661,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("sample_hops", &GpuSampler::sample_hops,
              py::call_guard<py::gil_scoped_release>(),
              "fused multi-hop sample+reindex, one sync per batch")
+        .def("sample_hops_ptr", &GpuSampler::sample_hops_ptr,
+             py::call_guard<py::gil_scoped_release>(),
+             "sample_hops plus each hop's dst segment pointer")
         .def("sample_hops_raw", &GpuSampler::sample_hops_raw,
              py::call_guard<py::gil_scoped_release>(),
              "zero-sync variant: ub-sized tensors + device sizes vector")
@@ -1669,6 +1741,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::call_guard<py::gil_scoped_release>());
     m.def("segment_mean_gather_backward", &segment_mean_gather_backward,
           py::call_guard<py::gil_scoped_release>());
+    m.def("segment_mean_prefix_backward", &segment_mean_prefix_backward,
+          py::arg("grad_agg"), py::arg("grad_self"), py::arg("src"),
+          py::arg("dst_ptr"), py::arg("n_src"));
+    m.def("segment_mean_lanes", &qk::segment_mean_lanes, py::arg("dim"),
+          py::arg("bf16") = false);
+    m.def("segment_mean_rows_in_flight", &qk::segment_mean_rows_in_flight);
 
     m.def("tall_gemm", &tall_gemm,
           "C[M,N] = A[M,K] @ B[K,N] (+bias), M huge, MFMA 32x32 tiles");

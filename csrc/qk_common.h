@@ -43,7 +43,10 @@ constexpr int kWaveSize = 64;  // CDNA4 wavefront
 // zeroed so downstream scans stay exact).
 void launch_capped_degree(hipStream_t s, const int64_t* indptr,
                           const int64_t* seeds, int64_t n, int k,
-                          int64_t* capped, const int64_t* n_dev = nullptr);
+                          int64_t* capped, const int64_t* n_dev = nullptr,
+                          bool zero_extra_slot = false);
+// zero_extra_slot: `capped` has n + 1 slots and capped[n] is set to 0, so
+// an exclusive scan over n + 1 counts ends in the total.
 
 // Exclusive scan over n int64 values; also writes total = sum to d_total.
 // temp_bytes(n) tells the caller how much scratch to allocate.
@@ -195,6 +198,15 @@ void launch_segment_mean_bwd_bf16(hipStream_t s, const void* grad_out,
 void launch_segment_mean_bwd(hipStream_t s, const float* grad_out,
                              const int64_t* src, const int64_t* dst_ptr,
                              int64_t n_dst, int64_t dim, float* grad_x);
+// lanes per dst segment the kernels above use for a row of `dim` channels,
+// and how many gathered rows the forward keeps in flight per segment
+int segment_mean_lanes(int64_t dim, bool bf16);
+int segment_mean_rows_in_flight();
+// out[0:head_bytes] = head, out[head_bytes:total_bytes] = 0 (one store
+// pass; sizes multiples of 4, out 16-byte aligned, head may be null when
+// head_bytes == 0)
+void launch_prefix_fill(hipStream_t s, const void* head, int64_t head_bytes,
+                        int64_t total_bytes, void* out);
 
 // Weighted segment sum (GAT attention aggregation), x [n_src, H*C],
 // w [n_edges, H] (per-edge per-head attention):

@@ -39,10 +39,13 @@ __global__ void capped_degree_kernel(const int64_t* __restrict__ indptr,
                                      const int64_t* __restrict__ seeds,
                                      int64_t n, int k,
                                      int64_t* __restrict__ capped,
-                                     const int64_t* __restrict__ n_dev) {
+                                     const int64_t* __restrict__ n_dev,
+                                     bool zero_extra_slot) {
     const int64_t nn = n_dev ? *n_dev : n;
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    // capped[n]: a zero count past the last seed (seeds[n] is never read)
+    if (zero_extra_slot && i == 0) capped[n] = 0;
     for (; i < n; i += stride) {
         if (i >= nn) {          // slack: keep the downstream scan exact
             capped[i] = 0;
@@ -185,10 +188,11 @@ inline int grid_for(int64_t work_items, int per_block) {
 
 void launch_capped_degree(hipStream_t s, const int64_t* indptr,
                           const int64_t* seeds, int64_t n, int k,
-                          int64_t* capped, const int64_t* n_dev) {
-    if (n == 0) return;
+                          int64_t* capped, const int64_t* n_dev,
+                          bool zero_extra_slot) {
+    if (n == 0 && !zero_extra_slot) return;
     capped_degree_kernel<<<grid_for(n, BLOCK), BLOCK, 0, s>>>(
-        indptr, seeds, n, k, capped, n_dev);
+        indptr, seeds, n, k, capped, n_dev, zero_extra_slot);
     QK_CHECK_HIP(hipGetLastError());
 }
 

@@ -10,6 +10,10 @@
 // Backward: grad_x[src[e]] += grad_out[d] / deg(d)  (device-scope f32
 // atomics; layer-1 input features skip it entirely since they carry no
 // grad).
+//
+// The segment-mean kernels size their lane group to the row (the smallest
+// power of two of lanes covering dim/4 fp32 or dim/8 bf16 channels, at
+// most one wave) and keep up to 8 gathered rows in flight per group.
 #include <hip/hip_bf16.h>
 
 #include "qk_common.h"
@@ -56,172 +60,278 @@ template <> struct vec4io<__hip_bfloat16> {
     }
 };
 
+// ---- segment mean: lane group sized to the row ---------------------------
+// One group of LANES lanes per dst, LANES = smallest power of two with
+// LANES * VPL >= dim (capped at a wave).  The group loads its segment's
+// src ids one per lane, broadcasts them by shuffle, and issues the row
+// loads of up to MEAN_U edges back to back before the first add, so a
+// segment costs ~len/MEAN_U memory round trips instead of len.  The adds
+// themselves stay in ascending edge order (fp32), then one multiply by
+// 1/count: bitwise the result of a one-row-at-a-time loop.
+
+constexpr int MEAN_U = 8;  // rows in flight per group
+
+inline int lanes_for(int64_t dim, int vpl) {
+    const int64_t need = (dim + vpl - 1) / vpl;
+    int lanes = 1;
+    while (lanes < need && lanes < 64) lanes <<= 1;
+    return lanes;
+}
+
+// Per-lane chunk of a feature row: VPL channels held as raw_t while in
+// flight (bf16 stays packed), accumulated in fp32.  `w` = valid channels
+// of this lane's chunk (VPL except at the row's end).
+template <typename T> struct rowio;
+template <> struct rowio<float> {
+    static constexpr int VPL = 4;
+    using raw_t = float4;
+    static __device__ __forceinline__ raw_t load(const float* p, int w,
+                                                 int64_t dim) {
+        if (w == VPL && (dim & 3) == 0)
+            return *reinterpret_cast<const float4*>(p);
+        raw_t r{0.f, 0.f, 0.f, 0.f};
+        if (w > 0) r.x = p[0];
+        if (w > 1) r.y = p[1];
+        if (w > 2) r.z = p[2];
+        if (w > 3) r.w = p[3];
+        return r;
+    }
+    static __device__ __forceinline__ void add(float acc[VPL],
+                                               const raw_t& r) {
+        acc[0] += r.x; acc[1] += r.y; acc[2] += r.z; acc[3] += r.w;
+    }
+    static __device__ __forceinline__ void store(float* p,
+                                                 const float acc[VPL],
+                                                 float inv, int w,
+                                                 int64_t dim) {
+        if (w == VPL && (dim & 3) == 0) {
+            *reinterpret_cast<float4*>(p) = float4{
+                acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv};
+        } else {
+            for (int q = 0; q < w; ++q) p[q] = acc[q] * inv;
+        }
+    }
+};
+template <> struct rowio<__hip_bfloat16> {
+    static constexpr int VPL = 8;
+    using raw_t = uint4;  // 8 bf16, two per dword
+    static __device__ __forceinline__ raw_t load(const __hip_bfloat16* p,
+                                                 int w, int64_t dim) {
+        // widest load the row alignment allows: dim % 8 -> 16 B,
+        // dim % 4 -> 8 B, even dim -> 4 B
+        if (w == VPL && (dim & 7) == 0)
+            return *reinterpret_cast<const uint4*>(p);
+        if (w == VPL && (dim & 3) == 0) {
+            const uint2 a = *reinterpret_cast<const uint2*>(p);
+            const uint2 b = *reinterpret_cast<const uint2*>(p + 4);
+            return uint4{a.x, a.y, b.x, b.y};
+        }
+        if (w == VPL && (dim & 1) == 0) {
+            const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+            return uint4{q[0], q[1], q[2], q[3]};
+        }
+        const uint16_t* h = reinterpret_cast<const uint16_t*>(p);
+        uint32_t e[VPL];
+#pragma unroll
+        for (int q = 0; q < VPL; ++q) e[q] = q < w ? (uint32_t)h[q] : 0u;
+        return uint4{e[0] | (e[1] << 16), e[2] | (e[3] << 16),
+                     e[4] | (e[5] << 16), e[6] | (e[7] << 16)};
+    }
+    static __device__ __forceinline__ void add2(float* acc, uint32_t v) {
+        acc[0] += __uint_as_float(v << 16);
+        acc[1] += __uint_as_float(v & 0xffff0000u);
+    }
+    static __device__ __forceinline__ void add(float acc[VPL],
+                                               const raw_t& r) {
+        add2(acc, r.x); add2(acc + 2, r.y);
+        add2(acc + 4, r.z); add2(acc + 6, r.w);
+    }
+    static __device__ __forceinline__ void store(__hip_bfloat16* p,
+                                                 const float acc[VPL],
+                                                 float inv, int w,
+                                                 int64_t dim) {
+        if (w == VPL && (dim & 1) == 0) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                *reinterpret_cast<__hip_bfloat162*>(p + 2 * i) =
+                    __float22bfloat162_rn(float2{acc[2 * i] * inv,
+                                                 acc[2 * i + 1] * inv});
+        } else {
+            for (int q = 0; q < w; ++q)
+                p[q] = (__hip_bfloat16)(acc[q] * inv);
+        }
+    }
+};
+
+template <typename T, int LANES>
 __global__ void __launch_bounds__(BLOCK)
-segment_mean_fwd_kernel(const float* __restrict__ x,
+segment_mean_fwd_kernel(const T* __restrict__ x,
                         const int64_t* __restrict__ src,
                         const int64_t* __restrict__ dst_ptr, int64_t n_dst,
-                        int64_t dim, float* __restrict__ out) {
-    const int sub_id = threadIdx.x / SUB;
-    const int lane = threadIdx.x % SUB;
-    int64_t d = (int64_t)blockIdx.x * ROWS_PER_BLOCK + sub_id;
-    const int64_t stride = (int64_t)gridDim.x * ROWS_PER_BLOCK;
+                        int64_t dim, T* __restrict__ out) {
+    using io = rowio<T>;
+    using raw_t = typename io::raw_t;
+    constexpr int VPL = io::VPL;
+    constexpr int GROUPS = BLOCK / LANES;
+    constexpr int U = MEAN_U;
+    const int lane = threadIdx.x % LANES;
+    int64_t d = (int64_t)blockIdx.x * GROUPS + threadIdx.x / LANES;
+    const int64_t stride = (int64_t)gridDim.x * GROUPS;
     for (; d < n_dst; d += stride) {
         const int64_t beg = dst_ptr[d], end = dst_ptr[d + 1];
         const float inv = (end > beg) ? 1.0f / (float)(end - beg) : 0.0f;
-        // lanes cover the feature dim in chunks of VPL floats
-        for (int64_t c = (int64_t)lane * VPL; c < dim; c += SUB * VPL) {
-            float acc[VPL] = {0.f, 0.f, 0.f, 0.f};
-            const int w = (int)min((int64_t)VPL, dim - c);
-            for (int64_t e = beg; e < end; ++e) {
-                const float* row = x + src[e] * dim + c;
-                if (w == VPL) {
-                    const float4 v = *reinterpret_cast<const float4*>(row);
-                    acc[0] += v.x; acc[1] += v.y; acc[2] += v.z; acc[3] += v.w;
-                } else {
-                    for (int q = 0; q < w; ++q) acc[q] += row[q];
+        // one pass unless the row is wider than a wave's 64 * VPL channels
+        for (int64_t c0 = 0; c0 < dim; c0 += LANES * VPL) {
+            const int64_t c = c0 + (int64_t)lane * VPL;
+            const int w = (int)max((int64_t)0, min((int64_t)VPL, dim - c));
+            float acc[VPL] = {};
+            for (int64_t eb = beg; eb < end; eb += LANES) {
+                // ids of the next LANES edges, one per lane
+                const int n = (int)min((int64_t)LANES, end - eb);
+                const int64_t my = lane < n ? src[eb + lane] : 0;
+                int j = 0;
+                for (; j + U <= n; j += U) {
+                    raw_t r[U];
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        const int64_t id = __shfl(my, j + u, LANES);
+                        if (w > 0) r[u] = io::load(x + id * dim + c, w, dim);
+                    }
+#pragma unroll
+                    for (int u = 0; u < U; ++u)
+                        if (w > 0) io::add(acc, r[u]);
+                }
+                if (j < n) {
+                    const int rem = n - j;  // 1 .. U-1, same for the group
+                    raw_t r[U - 1];
+#pragma unroll
+                    for (int u = 0; u < U - 1; ++u) {
+                        if (u < rem) {
+                            const int64_t id = __shfl(my, j + u, LANES);
+                            if (w > 0)
+                                r[u] = io::load(x + id * dim + c, w, dim);
+                        }
+                    }
+#pragma unroll
+                    for (int u = 0; u < U - 1; ++u)
+                        if (u < rem && w > 0) io::add(acc, r[u]);
                 }
             }
-            float* orow = out + d * dim + c;
-            if (w == VPL) {
-                float4 v{acc[0] * inv, acc[1] * inv, acc[2] * inv,
-                         acc[3] * inv};
-                *reinterpret_cast<float4*>(orow) = v;
-            } else {
-                for (int q = 0; q < w; ++q) orow[q] = acc[q] * inv;
-            }
+            if (w > 0) io::store(out + d * dim + c, acc, inv, w, dim);
         }
     }
 }
 
+// Backward scatter: grad_x[src[e]] += grad_out[d] / deg(d).  Same lane
+// group as the forward, but lanes own INTERLEAVED 4-byte words (word
+// k*LANES + lane), so one atomic wave-instruction covers 64 consecutive
+// words: 256 contiguous bytes of one row for a 256-float row, two 128-B
+// segments for 100 floats or 256 bf16.  bf16 uses the packed-bf16 atomic
+// on channel pairs (gradient buffer lives in ordinary HBM, no
+// system-scope requirement).
+template <typename T> struct atomio;
+template <> struct atomio<float> {
+    using word_t = float;
+    static constexpr int EPW = 1;  // elements per word
+    static __device__ __forceinline__ word_t scale(word_t g, float inv) {
+        return g * inv;
+    }
+    static __device__ __forceinline__ void add(word_t* p, word_t v) {
+        atomicAdd(p, v);
+    }
+};
+template <> struct atomio<__hip_bfloat16> {
+    using word_t = __hip_bfloat162;
+    static constexpr int EPW = 2;
+    static __device__ __forceinline__ word_t scale(word_t g, float inv) {
+        const float2 f = __bfloat1622float2(g);
+        return __float22bfloat162_rn(float2{f.x * inv, f.y * inv});
+    }
+    static __device__ __forceinline__ void add(word_t* p, word_t v) {
+        unsafeAtomicAdd(p, v);
+    }
+};
+
+template <typename T, int LANES>
 __global__ void __launch_bounds__(BLOCK)
-segment_mean_bwd_kernel(const float* __restrict__ grad_out,
+segment_mean_bwd_kernel(const T* __restrict__ grad_out,
                         const int64_t* __restrict__ src,
                         const int64_t* __restrict__ dst_ptr, int64_t n_dst,
-                        int64_t dim, float* __restrict__ grad_x) {
-    const int sub_id = threadIdx.x / SUB;
-    const int lane = threadIdx.x % SUB;
-    int64_t d = (int64_t)blockIdx.x * ROWS_PER_BLOCK + sub_id;
-    const int64_t stride = (int64_t)gridDim.x * ROWS_PER_BLOCK;
+                        int64_t dim, T* __restrict__ grad_x) {
+    using io = atomio<T>;
+    using word_t = typename io::word_t;
+    constexpr int K = 4;  // words per lane per pass
+    constexpr int GROUPS = BLOCK / LANES;
+    const int lane = threadIdx.x % LANES;
+    const int64_t words = dim / io::EPW;
+    int64_t d = (int64_t)blockIdx.x * GROUPS + threadIdx.x / LANES;
+    const int64_t stride = (int64_t)gridDim.x * GROUPS;
     for (; d < n_dst; d += stride) {
         const int64_t beg = dst_ptr[d], end = dst_ptr[d + 1];
         if (end <= beg) continue;
         const float inv = 1.0f / (float)(end - beg);
-        for (int64_t e = beg; e < end; ++e) {
-            float* grow = grad_x + src[e] * dim;
-            const float* orow = grad_out + d * dim;
-            for (int64_t c = lane; c < dim; c += SUB)
-                atomicAdd(&grow[c], orow[c] * inv);
-        }
-    }
-}
-
-// ---- bf16 variants of the segment mean (fp32 accumulate) ----------------
-// Feature rows load as 16-byte bf16x8 chunks; accumulation stays fp32 and
-// only the store rounds.  Backward uses the packed-bf16 global atomic
-// (flat_atomic_fadd_v2bf16) via HIP's unsafeAtomicAdd — fine here: the
-// gradient buffer lives in ordinary HBM (no system-scope requirement).
-
-constexpr int VPL_BF = 8;  // channels per lane chunk (4x bf16x2 loads:
-                           // 4B-aligned for any even dim; a 16B vector
-                           // would need dim % 8 == 0)
-
-__global__ void __launch_bounds__(BLOCK)
-segment_mean_fwd_bf16_kernel(const __hip_bfloat16* __restrict__ x,
-                             const int64_t* __restrict__ src,
-                             const int64_t* __restrict__ dst_ptr,
-                             int64_t n_dst, int64_t dim,
-                             __hip_bfloat16* __restrict__ out) {
-    const int sub_id = threadIdx.x / SUB;
-    const int lane = threadIdx.x % SUB;
-    int64_t d = (int64_t)blockIdx.x * ROWS_PER_BLOCK + sub_id;
-    const int64_t stride = (int64_t)gridDim.x * ROWS_PER_BLOCK;
-    for (; d < n_dst; d += stride) {
-        const int64_t beg = dst_ptr[d], end = dst_ptr[d + 1];
-        const float inv = (end > beg) ? 1.0f / (float)(end - beg) : 0.0f;
-        for (int64_t c = (int64_t)lane * VPL_BF; c < dim; c += SUB * VPL_BF) {
-            float acc[VPL_BF] = {};
-            const int w = (int)min((int64_t)VPL_BF, dim - c);
-            // dim % 4 == 0 makes every row base 8-byte aligned: use two
-            // bf16x4 loads per 8-channel chunk instead of four bf16x2
-            const bool v8 = (dim & 3) == 0;
-            for (int64_t e = beg; e < end; ++e) {
-                const __hip_bfloat16* row = x + src[e] * dim + c;
-                if (w == VPL_BF && v8) {
+        const T* orow = grad_out + d * dim;
+        for (int64_t c0 = 0; c0 < words; c0 += LANES * K) {
+            const int64_t cl = c0 + lane;
+            word_t g[K];
 #pragma unroll
-                    for (int i = 0; i < 2; ++i) {
-                        struct alignas(8) bf16x4v {
-                            __hip_bfloat162 lo, hi;
-                        };
-                        const bf16x4v v4 =
-                            *reinterpret_cast<const bf16x4v*>(row + 4 * i);
-                        const float2 f0 = __bfloat1622float2(v4.lo);
-                        const float2 f1 = __bfloat1622float2(v4.hi);
-                        acc[4 * i] += f0.x;
-                        acc[4 * i + 1] += f0.y;
-                        acc[4 * i + 2] += f1.x;
-                        acc[4 * i + 3] += f1.y;
-                    }
-                } else if (w == VPL_BF) {
+            for (int k = 0; k < K; ++k)
+                if (cl + k * LANES < words)
+                    g[k] = io::scale(
+                        reinterpret_cast<const word_t*>(orow)[cl + k * LANES],
+                        inv);
+            for (int64_t eb = beg; eb < end; eb += LANES) {
+                const int n = (int)min((int64_t)LANES, end - eb);
+                const int64_t my = lane < n ? src[eb + lane] : 0;
+                for (int j = 0; j < n; ++j) {
+                    const int64_t id = __shfl(my, j, LANES);
+                    word_t* grow =
+                        reinterpret_cast<word_t*>(grad_x + id * dim) + cl;
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const float2 f = __bfloat1622float2(
-                            *reinterpret_cast<const __hip_bfloat162*>(
-                                row + 2 * i));
-                        acc[2 * i] += f.x;
-                        acc[2 * i + 1] += f.y;
-                    }
-                } else {
-                    for (int q = 0; q < w; ++q) acc[q] += (float)row[q];
+                    for (int k = 0; k < K; ++k)
+                        if (cl + k * LANES < words)
+                            io::add(grow + k * LANES, g[k]);
                 }
             }
-            __hip_bfloat16* orow = out + d * dim + c;
-            if (w == VPL_BF) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    *reinterpret_cast<__hip_bfloat162*>(orow + 2 * i) =
-                        __float22bfloat162_rn(float2{acc[2 * i] * inv,
-                                                     acc[2 * i + 1] * inv});
-            } else {
-                for (int q = 0; q < w; ++q)
-                    orow[q] = (__hip_bfloat16)(acc[q] * inv);
-            }
         }
-    }
-}
-
-__global__ void __launch_bounds__(BLOCK)
-segment_mean_bwd_bf16_kernel(const __hip_bfloat16* __restrict__ grad_out,
-                             const int64_t* __restrict__ src,
-                             const int64_t* __restrict__ dst_ptr,
-                             int64_t n_dst, int64_t dim,
-                             __hip_bfloat16* __restrict__ grad_x) {
-    const int sub_id = threadIdx.x / SUB;
-    const int lane = threadIdx.x % SUB;
-    int64_t d = (int64_t)blockIdx.x * ROWS_PER_BLOCK + sub_id;
-    const int64_t stride = (int64_t)gridDim.x * ROWS_PER_BLOCK;
-    for (; d < n_dst; d += stride) {
-        const int64_t beg = dst_ptr[d], end = dst_ptr[d + 1];
-        if (end <= beg) continue;
-        const float inv = 1.0f / (float)(end - beg);
-        for (int64_t e = beg; e < end; ++e) {
-            __hip_bfloat16* grow = grad_x + src[e] * dim;
-            const __hip_bfloat16* orow = grad_out + d * dim;
-            // packed atomic: lanes own even channel pairs
-            for (int64_t c = 2 * lane; c + 1 < dim; c += 2 * SUB) {
-                const float2 g = __bfloat1622float2(
-                    *reinterpret_cast<const __hip_bfloat162*>(&orow[c]));
-                const __hip_bfloat162 add = __float22bfloat162_rn(
-                    float2{g.x * inv, g.y * inv});
-                unsafeAtomicAdd(reinterpret_cast<__hip_bfloat162*>(&grow[c]),
-                                add);
-            }
-            if (lane == 0 && (dim & 1)) {
+        if constexpr (io::EPW == 2) {
+            if ((dim & 1) && lane == 0) {
                 // odd tail channel
-                const float g = (float)orow[dim - 1] * inv;
-                unsafeAtomicAdd(&grow[dim - 1], (__hip_bfloat16)g);
+                const __hip_bfloat16 g =
+                    (__hip_bfloat16)((float)orow[dim - 1] * inv);
+                for (int64_t e = beg; e < end; ++e)
+                    unsafeAtomicAdd(&grad_x[src[e] * dim + dim - 1], g);
             }
         }
     }
+}
+
+// Input gradient of a layer whose x feeds both the aggregation and the
+// self path x[:n_self]: the first head_words 4-byte words of grad_x are
+// the self-path gradient, the rest zero.  One plain 16-B store pass; the
+// scatter kernel then adds the aggregation's part on the same stream.
+__global__ void __launch_bounds__(BLOCK)
+prefix_fill_kernel(const uint32_t* __restrict__ head, int64_t head_words,
+                   bool head_vec, int64_t total_words,
+                   uint32_t* __restrict__ out) {
+    const int64_t nvec = total_words / 4;
+    const int64_t t0 = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * BLOCK;
+    for (int64_t i = t0; i < nvec; i += stride) {
+        const int64_t w0 = i * 4;
+        uint4 v{0u, 0u, 0u, 0u};
+        if (head_vec && w0 + 4 <= head_words) {
+            v = reinterpret_cast<const uint4*>(head)[i];
+        } else if (w0 < head_words) {
+            v.x = head[w0];
+            if (w0 + 1 < head_words) v.y = head[w0 + 1];
+            if (w0 + 2 < head_words) v.z = head[w0 + 2];
+            if (w0 + 3 < head_words) v.w = head[w0 + 3];
+        }
+        reinterpret_cast<uint4*>(out)[i] = v;
+    }
+    for (int64_t w = nvec * 4 + t0; w < total_words; w += stride)
+        out[w] = w < head_words ? head[w] : 0u;
 }
 
 // ---- weighted segment sum (GAT attention aggregation) -------------------
@@ -599,12 +709,32 @@ inline int grid_for(int64_t work, int per_block) {
 
 }  // namespace
 
+// instantiate the lane-group width picked by lanes_for()
+#define QK_MEAN_DISPATCH(KERNEL, T, lanes, ...)                              \
+    switch (lanes) {                                                         \
+    case 1: KERNEL<T, 1><<<grid_for(n_dst, BLOCK / 1), BLOCK, 0, s>>>(__VA_ARGS__); break;   \
+    case 2: KERNEL<T, 2><<<grid_for(n_dst, BLOCK / 2), BLOCK, 0, s>>>(__VA_ARGS__); break;   \
+    case 4: KERNEL<T, 4><<<grid_for(n_dst, BLOCK / 4), BLOCK, 0, s>>>(__VA_ARGS__); break;   \
+    case 8: KERNEL<T, 8><<<grid_for(n_dst, BLOCK / 8), BLOCK, 0, s>>>(__VA_ARGS__); break;   \
+    case 16: KERNEL<T, 16><<<grid_for(n_dst, BLOCK / 16), BLOCK, 0, s>>>(__VA_ARGS__); break; \
+    case 32: KERNEL<T, 32><<<grid_for(n_dst, BLOCK / 32), BLOCK, 0, s>>>(__VA_ARGS__); break; \
+    default: KERNEL<T, 64><<<grid_for(n_dst, BLOCK / 64), BLOCK, 0, s>>>(__VA_ARGS__); break; \
+    }
+
+int segment_mean_lanes(int64_t dim, bool bf16) {
+    return lanes_for(dim, bf16 ? rowio<__hip_bfloat16>::VPL
+                               : rowio<float>::VPL);
+}
+
+int segment_mean_rows_in_flight() { return MEAN_U; }
+
 void launch_segment_mean_fwd(hipStream_t s, const float* x,
                              const int64_t* src, const int64_t* dst_ptr,
                              int64_t n_dst, int64_t dim, float* out) {
     if (n_dst == 0) return;
-    segment_mean_fwd_kernel<<<grid_for(n_dst, ROWS_PER_BLOCK), BLOCK, 0, s>>>(
-        x, src, dst_ptr, n_dst, dim, out);
+    QK_MEAN_DISPATCH(segment_mean_fwd_kernel, float,
+                     segment_mean_lanes(dim, false), x, src, dst_ptr, n_dst,
+                     dim, out);
     QK_CHECK_HIP(hipGetLastError());
 }
 
@@ -612,8 +742,9 @@ void launch_segment_mean_bwd(hipStream_t s, const float* grad_out,
                              const int64_t* src, const int64_t* dst_ptr,
                              int64_t n_dst, int64_t dim, float* grad_x) {
     if (n_dst == 0) return;
-    segment_mean_bwd_kernel<<<grid_for(n_dst, ROWS_PER_BLOCK), BLOCK, 0, s>>>(
-        grad_out, src, dst_ptr, n_dst, dim, grad_x);
+    QK_MEAN_DISPATCH(segment_mean_bwd_kernel, float,
+                     segment_mean_lanes(dim, false), grad_out, src, dst_ptr,
+                     n_dst, dim, grad_x);
     QK_CHECK_HIP(hipGetLastError());
 }
 
@@ -621,10 +752,9 @@ void launch_segment_mean_fwd_bf16(hipStream_t s, const void* x,
                                   const int64_t* src, const int64_t* dst_ptr,
                                   int64_t n_dst, int64_t dim, void* out) {
     if (n_dst == 0) return;
-    segment_mean_fwd_bf16_kernel<<<grid_for(n_dst, ROWS_PER_BLOCK), BLOCK, 0,
-                                   s>>>((const __hip_bfloat16*)x, src,
-                                        dst_ptr, n_dst, dim,
-                                        (__hip_bfloat16*)out);
+    QK_MEAN_DISPATCH(segment_mean_fwd_kernel, __hip_bfloat16,
+                     segment_mean_lanes(dim, true), (const __hip_bfloat16*)x,
+                     src, dst_ptr, n_dst, dim, (__hip_bfloat16*)out);
     QK_CHECK_HIP(hipGetLastError());
 }
 
@@ -632,10 +762,27 @@ void launch_segment_mean_bwd_bf16(hipStream_t s, const void* grad_out,
                                   const int64_t* src, const int64_t* dst_ptr,
                                   int64_t n_dst, int64_t dim, void* grad_x) {
     if (n_dst == 0) return;
-    segment_mean_bwd_bf16_kernel<<<grid_for(n_dst, ROWS_PER_BLOCK), BLOCK, 0,
-                                   s>>>((const __hip_bfloat16*)grad_out, src,
-                                        dst_ptr, n_dst, dim,
-                                        (__hip_bfloat16*)grad_x);
+    QK_MEAN_DISPATCH(segment_mean_bwd_kernel, __hip_bfloat16,
+                     segment_mean_lanes(dim, true),
+                     (const __hip_bfloat16*)grad_out, src, dst_ptr, n_dst,
+                     dim, (__hip_bfloat16*)grad_x);
+    QK_CHECK_HIP(hipGetLastError());
+}
+
+#undef QK_MEAN_DISPATCH
+
+void launch_prefix_fill(hipStream_t s, const void* head, int64_t head_bytes,
+                        int64_t total_bytes, void* out) {
+    if (total_bytes == 0) return;
+    if (head_bytes % 4 || total_bytes % 4 || head_bytes > total_bytes ||
+        (uintptr_t)out % 16 || (uintptr_t)head % 4)
+        throw std::runtime_error(
+            "prefix_fill: sizes must be multiples of 4 bytes, head within "
+            "the output, output 16-byte aligned");
+    const int64_t total_words = total_bytes / 4;
+    prefix_fill_kernel<<<grid_for(total_words / 4 + 1, BLOCK), BLOCK, 0, s>>>(
+        (const uint32_t*)head, head_bytes / 4, (uintptr_t)head % 16 == 0,
+        total_words, (uint32_t*)out);
     QK_CHECK_HIP(hipGetLastError());
 }
 

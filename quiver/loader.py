@@ -22,6 +22,8 @@ from collections import deque
 
 import torch
 
+from .pyg.sage_sampler import DST_PTR_ATTR
+
 __all__ = ["TrainingPrefetcher"]
 
 
@@ -63,13 +65,15 @@ class _GraphedChain:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.stream(stream):
                 with torch.cuda.graph(g, stream=stream):
-                    raw, sizes_dev = sampler.quiver.sample_hops_raw(
+                    raw, sizes_dev, ptrs = sampler.quiver.sample_hops_raw(
                         static_seeds, sampler.sizes)
                     x_ub = None
                     if feature is not None:
                         n_dev = sizes_dev[2 * H - 1:2 * H]
                         x_ub = feature.gather_raw(raw[H - 1][0], n_dev)
-            tok = (static_seeds, raw, sizes_dev, sizes_pin)
+            # ptrs (per-hop dst segment pointers) are graph-pool buffers
+            # like raw: static lifetime, rewritten by every replay
+            tok = (static_seeds, raw, sizes_dev, sizes_pin, ptrs)
             self.slots.append((static_seeds, g, tok, x_ub))
 
     def run(self, seeds):
@@ -260,9 +264,15 @@ class TrainingPrefetcher:
                     # upper-bound buffers read on the main stream
                     for f_ub, e_ub in payload[1]:
                         e_ub.record_stream(cur)
+                    # so do the attached dst segment pointers
+                    for p_ub in payload[4]:
+                        p_ub.record_stream(cur)
                 n_id.record_stream(cur)
                 for adj in adjs:
                     adj.edge_index.record_stream(cur)
+                    ptr = getattr(adj.edge_index, DST_PTR_ATTR, None)
+                    if ptr is not None:
+                        ptr.record_stream(cur)
                 if x is not None:
                     x.record_stream(cur)
             # consumer launches the training step for this batch inside the

@@ -15,6 +15,10 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _ext
+# tensor attribute under which GraphSageSampler hangs a hop's segment
+# pointer on its edge_index (survives `for edge_index, _, size in adjs`,
+# not clone()/.to()/indexing)
+from .pyg.sage_sampler import DST_PTR_ATTR
 
 __all__ = ["SAGEConv", "GATConv", "GraphSAGE", "GAT", "QLinear"]
 
@@ -45,6 +49,38 @@ class _SegmentMeanAgg(torch.autograd.Function):
         grad_x = _ext.segment_mean_gather_backward(
             grad_out.contiguous(), src, dst_ptr, ctx.n_src)
         return grad_x, None, None
+
+
+class _SegmentMeanPrefix(torch.autograd.Function):
+    """Mean aggregation plus the self-path slice for the bipartite prefix
+    case (x_dst is x[:n_self]): returns (agg, x[:n_self]).
+
+    Autograd would otherwise assemble grad_x from a zero-filled scatter
+    target, a zero-padded slice gradient and a full-size add; here the
+    backward makes one native call that stores the self-path rows (zeros
+    below them) and scatters the aggregation's part on top.
+    """
+
+    @staticmethod
+    def forward(ctx, x, src, dst_ptr, n_self):
+        ctx.save_for_backward(src, dst_ptr)
+        ctx.n_src = x.size(0)
+        ctx.set_materialize_grads(False)
+        return (_ext.segment_mean_gather(x, src, dst_ptr),
+                x.narrow(0, 0, n_self))
+
+    @staticmethod
+    def backward(ctx, grad_agg, grad_self):
+        src, dst_ptr = ctx.saved_tensors
+        if grad_agg is None:
+            if grad_self is None:
+                return None, None, None, None
+            grad_x = grad_self.new_zeros((ctx.n_src, grad_self.size(1)))
+            grad_x[:grad_self.size(0)] = grad_self
+            return grad_x, None, None, None
+        grad_x = _ext.segment_mean_prefix_backward(
+            grad_agg.contiguous(), grad_self, src, dst_ptr, ctx.n_src)
+        return grad_x, None, None, None
 
 
 class _SegmentWSum(torch.autograd.Function):
@@ -215,16 +251,35 @@ def _dst_ptr_from_sorted(dst, n_dst):
     return torch.searchsorted(dst, _arange(n_dst + 1, dst.device))
 
 
-def _mean_aggregate(x_src, src, dst, n_dst, sorted_dst=False):
+def _dst_ptr_for(edge_index, n_dst):
+    """Segment pointer of a dst-sorted edge_index: the one the sampler
+    attached (its own scan of the per-dst sampled counts) when present and
+    of the right length, else rebuilt from the edge list."""
+    dst = edge_index[1]
+    ptr = getattr(edge_index, DST_PTR_ATTR, None)
+    if (ptr is None or ptr.dim() != 1 or ptr.numel() != n_dst + 1
+            or ptr.device != dst.device or ptr.dtype != torch.int64):
+        return _dst_ptr_from_sorted(dst, n_dst)
+    if _QUIVER_DEBUG:
+        assert torch.equal(ptr, _dst_ptr_from_sorted(dst, n_dst)), \
+            "sampler-attached dst_ptr disagrees with edge_index[1]"
+    return ptr
+
+
+def _fused_mean_ok(x_src, dst, sorted_dst):
+    return (sorted_dst and x_src.is_cuda and dst.numel() > 0
+            and (x_src.dtype == torch.float32
+                 or (x_src.dtype == torch.bfloat16
+                     and x_src.size(1) % 2 == 0)))
+
+
+def _mean_aggregate(x_src, src, dst, n_dst, sorted_dst=False, dst_ptr=None):
     """Mean of x_src[src] grouped by dst.  Uses the fused HIP kernel when
     the caller guarantees dst is sorted ascending (our sampler's layout)
     on fp32 GPU tensors."""
-    fused_ok = (sorted_dst and x_src.is_cuda and dst.numel() > 0
-                and (x_src.dtype == torch.float32
-                     or (x_src.dtype == torch.bfloat16
-                         and x_src.size(1) % 2 == 0)))
-    if fused_ok:
-        dst_ptr = _dst_ptr_from_sorted(dst, n_dst)
+    if _fused_mean_ok(x_src, dst, sorted_dst):
+        if dst_ptr is None:
+            dst_ptr = _dst_ptr_from_sorted(dst, n_dst)
         return _SegmentMeanAgg.apply(x_src, src, dst_ptr)
     agg = torch.zeros((n_dst, x_src.size(1)), dtype=x_src.dtype,
                       device=x_src.device)
@@ -260,8 +315,25 @@ class SAGEConv(nn.Module):
         src, dst = edge_index[0], edge_index[1]
         n_dst = x_dst.size(0) if size is None else int(size[1])
         # aggregate-then-project: segment mean on in_channels, one GEMM after
-        agg = _mean_aggregate(x_src, src, dst, n_dst,
-                              sorted_dst=self.sorted_dst)
+        if _fused_mean_ok(x_src, dst, self.sorted_dst):
+            dst_ptr = _dst_ptr_for(edge_index, n_dst)
+            prefix = (x_dst.data_ptr() == x_src.data_ptr()
+                      and x_dst.size(0) <= x_src.size(0)
+                      and x_dst.stride() == x_src.stride()
+                      and x_dst.size(1) == x_src.size(1)
+                      and x_src.is_contiguous())
+            if (prefix and x_src.requires_grad and torch.is_grad_enabled()):
+                # x feeds both paths: one function owns the whole input
+                # gradient (inputs without grad, e.g. layer 0, skip this
+                # and never run a backward)
+                agg, x_dst = _SegmentMeanPrefix.apply(x_src, src, dst_ptr,
+                                                      x_dst.size(0))
+            else:
+                agg = _mean_aggregate(x_src, src, dst, n_dst,
+                                      sorted_dst=True, dst_ptr=dst_ptr)
+        else:
+            agg = _mean_aggregate(x_src, src, dst, n_dst,
+                                  sorted_dst=self.sorted_dst)
         out = self.lin_l(agg)
         if (x_dst.is_cuda and x_dst.dtype == torch.float32
                 and x_dst.size(0) >= _WGRAD_MIN_K
@@ -342,7 +414,7 @@ class GATConv(nn.Module):
         fused = (self.sorted_dst and alpha_src.is_cuda
                  and alpha_src.dtype == torch.float32 and dst.numel() > 0)
         if fused:
-            dst_ptr = _dst_ptr_from_sorted(dst, n_dst)
+            dst_ptr = _dst_ptr_for(edge_index, n_dst)
             alpha = _GatAlpha.apply(alpha_src, alpha_dst, src, dst_ptr, H,
                                     self.negative_slope, src.numel())
         else:
@@ -368,7 +440,7 @@ class GATConv(nn.Module):
                 and dst.numel() > 0):
             # fused weighted segment sum over the dst-sorted edges
             if not fused:
-                dst_ptr = _dst_ptr_from_sorted(dst, n_dst)
+                dst_ptr = _dst_ptr_for(edge_index, n_dst)
             out = _SegmentWSum.apply(h_src.reshape(-1, H * C), alpha, src,
                                      dst_ptr, H)
             out = out if self.concat else out.view(n_dst, H, C).mean(1)

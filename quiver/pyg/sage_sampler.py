@@ -23,6 +23,19 @@ T = TypeVar("T")
 
 __all__ = ["GraphSageSampler", "MixedGraphSageSampler", "SampleJob", "Adj"]
 
+# attribute name, shared with quiver.nn and quiver.loader
+DST_PTR_ATTR = "_quiver_dst_ptr"
+
+
+def _attach_dst_ptr(edge_index, dst_ptr):
+    """Hang the hop's segment pointer (the sampler's own scan of the
+    per-dst sampled counts, n_dst + 1 entries) on edge_index so the
+    sorted_dst layers need no searchsorted.  A plain tensor attribute:
+    Adj stays a 3-tuple and consumers that copy edge_index simply fall
+    back to rebuilding the pointer."""
+    setattr(edge_index, DST_PTR_ATTR, dst_ptr)
+    return edge_index
+
 
 class Adj(NamedTuple):
     edge_index: torch.Tensor
@@ -116,9 +129,10 @@ class GraphSageSampler:
             # (the python per-hop loop cost ~12 stream syncs and ~40 torch
             # ops; the training step was launch-bound)
             with trace_scope("sampler.sample_hops"):
-                hops = self.quiver.sample_hops(nodes, self.sizes)
+                hops = self.quiver.sample_hops_ptr(nodes, self.sizes)
             prev_n = nodes.size(0)
-            for frontier, edge_index in hops:
+            for frontier, edge_index, dst_ptr in hops:
+                _attach_dst_ptr(edge_index, dst_ptr)
                 # edge_index is emitted by the native chain as one [2, m]
                 # tensor (edges[0]=src local, edges[1]=dst local): no
                 # stack copy here
@@ -168,11 +182,11 @@ class GraphSageSampler:
         if not isinstance(input_nodes, torch.Tensor):
             input_nodes = torch.tensor(input_nodes, dtype=torch.long)
         nodes = input_nodes.to(self.device)
-        raw, sizes_dev = self.quiver.sample_hops_raw(nodes, self.sizes)
+        raw, sizes_dev, ptrs = self.quiver.sample_hops_raw(nodes, self.sizes)
         sizes_pin = torch.empty(sizes_dev.numel(), dtype=torch.int64,
                                 pin_memory=True)
         sizes_pin.copy_(sizes_dev, non_blocking=True)
-        return (nodes, raw, sizes_dev, sizes_pin)
+        return (nodes, raw, sizes_dev, sizes_pin, ptrs)
 
     def sample_finalize(self, token):
         """Build (n_id, batch_size, adjs) from a sample_async token.
@@ -180,7 +194,8 @@ class GraphSageSampler:
         The caller must have synchronized with the producing stream (e.g.
         event.synchronize()) so the pinned sizes are valid.
         """
-        nodes, raw, _sizes_dev, sizes_pin = token
+        nodes, raw, _sizes_dev, sizes_pin = token[:4]
+        ptrs = token[4] if len(token) > 4 else None
         adjs = []
         prev = nodes.size(0)
         frontier = nodes
@@ -190,6 +205,10 @@ class GraphSageSampler:
             frontier = f_ub[:u]
             # zero-copy: a narrowed view of the upper-bound edge buffer
             edge_index = e_ub.narrow(1, 0, m)
+            if ptrs is not None:
+                # upper-bound-sized scan; its first prev + 1 entries are
+                # this hop's segment pointer
+                _attach_dst_ptr(edge_index, ptrs[h].narrow(0, 0, prev + 1))
             adjs.append(Adj(edge_index, torch.tensor([]),
                             torch.LongTensor([u, prev])))
             prev = u
