@@ -1186,82 +1186,117 @@ class ShardTensor {
 };
 
 // ---------------------------------------------------------------------------
-// Fused SAGE-mean aggregation over dst-sorted edges (segment_kernels.hip)
+// Message passing over dst-sorted edges (segment_kernels.hip)
 // ---------------------------------------------------------------------------
+
+// Front end of every segment / GAT binding: validates the feature (or
+// gradient) rows and the edge structure before anything is allocated or
+// launched, so a misplaced tensor is a Python error and never a bad
+// pointer in a kernel.  Nothing here reads device memory.  Holds the
+// contiguous tensors, makes their device current for the call and
+// launches on that device's current stream.
+struct SegmentCall {
+    const char* op;
+    torch::Tensor feat, src, dst_ptr;
+    int64_t n_dst = 0, dim;
+    qk::Elem elem;
+    DeviceScope scope;
+    hipStream_t stream;
+
+    // src / dst_ptr: null for ops that have none
+    SegmentCall(const char* op, const char* name, const torch::Tensor& f,
+                bool fp32_only, const torch::Tensor* src_in,
+                const torch::Tensor* dst_ptr_in)
+        : op(op), feat(checked_rows(op, name, f, fp32_only)),
+          dim(feat.size(1)),
+          elem(feat.scalar_type() == torch::kBFloat16 ? qk::Elem::bf16
+                                                      : qk::Elem::f32),
+          scope(feat.get_device()),
+          stream(c10::hip::getCurrentHIPStream(feat.get_device()).stream()) {
+        if (src_in)
+            src = arg("src", *src_in, torch::kInt64, {src_in->numel()});
+        if (dst_ptr_in) {
+            TORCH_CHECK(dst_ptr_in->numel() >= 1, op, ": dst_ptr is empty");
+            dst_ptr = arg("dst_ptr", *dst_ptr_in, torch::kInt64,
+                          {dst_ptr_in->numel()});
+            n_dst = dst_ptr.numel() - 1;
+        }
+    }
+
+    // a further tensor argument: on feat's device, dtype and shape given
+    // (src and dst_ptr: int64 and 1-D)
+    torch::Tensor arg(const char* name, const torch::Tensor& t,
+                      torch::ScalarType dtype, at::IntArrayRef shape) const {
+        TORCH_CHECK(t.device() == feat.device() && t.scalar_type() == dtype &&
+                    t.sizes() == shape,
+                    op, ": ", name, " must be ", dtype, " ", shape, " on ",
+                    feat.device(), ", got ", t.scalar_type(), " ", t.sizes(),
+                    " on ", t.device());
+        return t.contiguous();
+    }
+
+    // per-head channels of a row made of `heads` heads
+    int chead(int64_t heads) const {
+        TORCH_CHECK(heads > 0 && dim % heads == 0, op, ": feature dim ", dim,
+                    " is not a multiple of heads ", heads);
+        return (int)(dim / heads);
+    }
+
+    const int64_t* src_ptr() const { return src.data_ptr<int64_t>(); }
+    const int64_t* dst_ptr_ptr() const { return dst_ptr.data_ptr<int64_t>(); }
+
+  private:
+    static torch::Tensor checked_rows(const char* op, const char* name,
+                                      const torch::Tensor& t,
+                                      bool fp32_only) {
+        TORCH_CHECK(t.is_cuda() && t.dim() == 2 &&
+                    (t.scalar_type() == torch::kFloat32 ||
+                     (!fp32_only && t.scalar_type() == torch::kBFloat16)),
+                    op, ": ", name, " must be a 2-D CUDA tensor of ",
+                    fp32_only ? "float32" : "float32 or bfloat16", ", got ",
+                    t.scalar_type(), " ", t.sizes(), " on ", t.device());
+        return t.contiguous();
+    }
+};
+
+// out[d] = mean of x[src[e]] over segment d
 torch::Tensor segment_mean_gather(torch::Tensor x, torch::Tensor src,
                                   torch::Tensor dst_ptr) {
-    TORCH_CHECK(x.is_cuda() && x.dim() == 2 &&
-                (x.dtype() == torch::kFloat32 ||
-                 x.dtype() == torch::kBFloat16));
-    x = x.contiguous();
-    src = src.contiguous();
-    dst_ptr = dst_ptr.contiguous();
-    int64_t n_dst = dst_ptr.numel() - 1;
-    auto out = torch::empty({n_dst, x.size(1)}, x.options());
-    if (x.dtype() == torch::kBFloat16) {
-        TORCH_CHECK(x.size(1) % 2 == 0,
-                    "bf16 segment mean needs an even feature dim");
-        qk::launch_segment_mean_fwd_bf16(
-            current_stream(), x.data_ptr(), src.data_ptr<int64_t>(),
-            dst_ptr.data_ptr<int64_t>(), n_dst, x.size(1), out.data_ptr());
-        return out;
-    }
-    qk::launch_segment_mean_fwd(current_stream(), x.data_ptr<float>(),
-                                src.data_ptr<int64_t>(),
-                                dst_ptr.data_ptr<int64_t>(), n_dst, x.size(1),
-                                out.data_ptr<float>());
+    SegmentCall c("segment_mean_gather", "x", x, false, &src, &dst_ptr);
+    auto out = torch::empty({c.n_dst, c.dim}, c.feat.options());
+    qk::launch_segment_mean_fwd(c.stream, c.elem, c.feat.data_ptr(),
+                                c.src_ptr(), c.dst_ptr_ptr(), c.n_dst, c.dim,
+                                out.data_ptr());
     return out;
 }
 
 // grad_x [n_src, D] = scatter of grad_out over the edges, on top of
 // `grad_self` in the leading rows (or zeros when grad_self is absent).
 static torch::Tensor segment_mean_backward_onto(
-    torch::Tensor grad_out, const c10::optional<torch::Tensor>& grad_self,
-    torch::Tensor src, torch::Tensor dst_ptr, int64_t n_src) {
-    TORCH_CHECK(grad_out.is_cuda() && grad_out.dim() == 2 &&
-                (grad_out.dtype() == torch::kFloat32 ||
-                 grad_out.dtype() == torch::kBFloat16));
-    grad_out = grad_out.contiguous();
-    src = src.contiguous();
-    dst_ptr = dst_ptr.contiguous();
-    int64_t n_dst = dst_ptr.numel() - 1;
-    const int64_t dim = grad_out.size(1);
-    TORCH_CHECK(grad_out.size(0) == n_dst,
-                "segment mean backward: grad_out rows != dst_ptr segments");
-    auto grad_x = torch::empty({n_src, dim}, grad_out.options());
-    const int64_t row_bytes = dim * (int64_t)grad_out.element_size();
+    const char* op, torch::Tensor grad_out,
+    const c10::optional<torch::Tensor>& grad_self, torch::Tensor src,
+    torch::Tensor dst_ptr, int64_t n_src) {
+    SegmentCall c(op, "grad_out", grad_out, false, &src, &dst_ptr);
+    TORCH_CHECK(c.feat.size(0) == c.n_dst, op, ": grad_out has ",
+                c.feat.size(0), " rows for ", c.n_dst, " dst_ptr segments");
+    const int64_t row_bytes = c.dim * (int64_t)c.feat.element_size();
     const void* head = nullptr;
     int64_t head_bytes = 0;
     torch::Tensor gs;
     if (grad_self.has_value() && grad_self->defined()) {
-        gs = grad_self->contiguous();
-        TORCH_CHECK(gs.dim() == 2 && gs.size(1) == dim &&
-                    gs.size(0) <= n_src && gs.dtype() == grad_out.dtype() &&
-                    gs.device() == grad_out.device(),
-                    "segment mean backward: self-path gradient must be "
-                    "[<= n_src, D] of grad_out's dtype and device");
+        TORCH_CHECK(grad_self->dim() == 2 && grad_self->size(0) <= n_src, op,
+                    ": grad_self must have at most n_src rows");
+        gs = c.arg("grad_self", *grad_self, c.feat.scalar_type(),
+                   {grad_self->size(0), c.dim});
         head = gs.data_ptr();
         head_bytes = gs.size(0) * row_bytes;
     }
-    if (grad_out.dtype() == torch::kBFloat16)
-        TORCH_CHECK(dim % 2 == 0,
-                    "bf16 segment mean needs an even feature dim");
-    qk::launch_prefix_fill(current_stream(), head, head_bytes,
-                           n_src * row_bytes, grad_x.data_ptr());
-    if (grad_out.dtype() == torch::kBFloat16) {
-        TORCH_CHECK(grad_out.size(1) % 2 == 0,
-                    "bf16 segment mean needs an even feature dim");
-        qk::launch_segment_mean_bwd_bf16(
-            current_stream(), grad_out.data_ptr(), src.data_ptr<int64_t>(),
-            dst_ptr.data_ptr<int64_t>(), n_dst, grad_out.size(1),
-            grad_x.data_ptr());
-        return grad_x;
-    }
-    qk::launch_segment_mean_bwd(current_stream(),
-                                grad_out.data_ptr<float>(),
-                                src.data_ptr<int64_t>(),
-                                dst_ptr.data_ptr<int64_t>(), n_dst,
-                                grad_out.size(1), grad_x.data_ptr<float>());
+    auto grad_x = torch::empty({n_src, c.dim}, c.feat.options());
+    qk::launch_prefix_fill(c.stream, head, head_bytes, n_src * row_bytes,
+                           grad_x.data_ptr());
+    qk::launch_segment_mean_bwd(c.stream, c.elem, c.feat.data_ptr(),
+                                c.src_ptr(), c.dst_ptr_ptr(), c.n_dst, c.dim,
+                                grad_x.data_ptr());
     return grad_x;
 }
 
@@ -1269,7 +1304,8 @@ torch::Tensor segment_mean_gather_backward(torch::Tensor grad_out,
                                            torch::Tensor src,
                                            torch::Tensor dst_ptr,
                                            int64_t n_src) {
-    return segment_mean_backward_onto(grad_out, c10::nullopt, src, dst_ptr,
+    return segment_mean_backward_onto("segment_mean_gather_backward",
+                                      grad_out, c10::nullopt, src, dst_ptr,
                                       n_src);
 }
 
@@ -1280,7 +1316,8 @@ torch::Tensor segment_mean_gather_backward(torch::Tensor grad_out,
 torch::Tensor segment_mean_prefix_backward(
     torch::Tensor grad_agg, c10::optional<torch::Tensor> grad_self,
     torch::Tensor src, torch::Tensor dst_ptr, int64_t n_src) {
-    return segment_mean_backward_onto(grad_agg, grad_self, src, dst_ptr,
+    return segment_mean_backward_onto("segment_mean_prefix_backward",
+                                      grad_agg, grad_self, src, dst_ptr,
                                       n_src);
 }
 
@@ -1315,30 +1352,14 @@ std::tuple<torch::Tensor, torch::Tensor> wgrad(torch::Tensor a,
 torch::Tensor segment_wsum(torch::Tensor x, torch::Tensor w,
                            torch::Tensor src, torch::Tensor dst_ptr,
                            int64_t heads) {
-    TORCH_CHECK(x.is_cuda() && x.dim() == 2 &&
-                (x.dtype() == torch::kFloat32 ||
-                 x.dtype() == torch::kBFloat16));
-    TORCH_CHECK(w.is_cuda() && w.dtype() == torch::kFloat32 && w.dim() == 2 &&
-                w.size(1) == heads);
-    x = x.contiguous();
-    w = w.contiguous();
-    src = src.contiguous();
-    dst_ptr = dst_ptr.contiguous();
-    int64_t n_dst = dst_ptr.numel() - 1;
-    int chead = (int)(x.size(1) / heads);
-    TORCH_CHECK((int64_t)chead * heads == x.size(1), "dim % heads != 0");
-    auto out = torch::empty({n_dst, x.size(1)}, x.options());
-    if (x.dtype() == torch::kBFloat16) {
-        qk::launch_segment_wsum_fwd_bf16(
-            current_stream(), x.data_ptr(), w.data_ptr<float>(),
-            src.data_ptr<int64_t>(), dst_ptr.data_ptr<int64_t>(), n_dst,
-            (int)heads, chead, out.data_ptr());
-        return out;
-    }
-    qk::launch_segment_wsum_fwd(current_stream(), x.data_ptr<float>(),
-                                w.data_ptr<float>(), src.data_ptr<int64_t>(),
-                                dst_ptr.data_ptr<int64_t>(), n_dst,
-                                (int)heads, chead, out.data_ptr<float>());
+    SegmentCall c("segment_wsum", "x", x, false, &src, &dst_ptr);
+    const int chead = c.chead(heads);
+    w = c.arg("w", w, torch::kFloat32, {c.src.numel(), heads});
+    auto out = torch::empty({c.n_dst, c.dim}, c.feat.options());
+    qk::launch_segment_wsum_fwd(c.stream, c.elem, c.feat.data_ptr(),
+                                w.data_ptr<float>(), c.src_ptr(),
+                                c.dst_ptr_ptr(), c.n_dst, (int)heads, chead,
+                                out.data_ptr());
     return out;
 }
 
@@ -1346,46 +1367,25 @@ std::tuple<torch::Tensor, torch::Tensor> segment_wsum_backward(
     torch::Tensor grad_out, torch::Tensor x, torch::Tensor w,
     torch::Tensor src, torch::Tensor dst_ptr, int64_t heads,
     bool need_gx, bool need_gw) {
-    grad_out = grad_out.contiguous();
-    x = x.contiguous();
-    w = w.contiguous();
-    src = src.contiguous();
-    dst_ptr = dst_ptr.contiguous();
-    int64_t n_dst = dst_ptr.numel() - 1;
-    int chead = (int)(x.size(1) / heads);
-    const bool bf16 = x.dtype() == torch::kBFloat16;
+    SegmentCall c("segment_wsum_backward", "x", x, false, &src, &dst_ptr);
+    const int chead = c.chead(heads);
+    grad_out = c.arg("grad_out", grad_out, c.feat.scalar_type(),
+                     {c.n_dst, c.dim});
+    w = c.arg("w", w, torch::kFloat32, {c.src.numel(), heads});
     torch::Tensor gx, gw;
     if (need_gx) {
-        gx = torch::zeros_like(x);
-        if (bf16) {
-            TORCH_CHECK(((int64_t)chead * heads) % 2 == 0,
-                        "bf16 wsum needs an even dim");
-            qk::launch_segment_wsum_bwd_x_bf16(
-                current_stream(), grad_out.data_ptr(), w.data_ptr<float>(),
-                src.data_ptr<int64_t>(), dst_ptr.data_ptr<int64_t>(), n_dst,
-                (int)heads, chead, gx.data_ptr());
-        } else {
-            qk::launch_segment_wsum_bwd_x(
-                current_stream(), grad_out.data_ptr<float>(),
-                w.data_ptr<float>(), src.data_ptr<int64_t>(),
-                dst_ptr.data_ptr<int64_t>(), n_dst, (int)heads, chead,
-                gx.data_ptr<float>());
-        }
+        gx = torch::zeros_like(c.feat);
+        qk::launch_segment_wsum_bwd_x(c.stream, c.elem, grad_out.data_ptr(),
+                                      w.data_ptr<float>(), c.src_ptr(),
+                                      c.dst_ptr_ptr(), c.n_dst, (int)heads,
+                                      chead, gx.data_ptr());
     }
     if (need_gw) {
         gw = torch::empty_like(w);
-        if (bf16) {
-            qk::launch_segment_wsum_bwd_w_bf16(
-                current_stream(), grad_out.data_ptr(), x.data_ptr(),
-                src.data_ptr<int64_t>(), dst_ptr.data_ptr<int64_t>(), n_dst,
-                (int)heads, chead, gw.data_ptr<float>());
-        } else {
-            qk::launch_segment_wsum_bwd_w(
-                current_stream(), grad_out.data_ptr<float>(),
-                x.data_ptr<float>(), src.data_ptr<int64_t>(),
-                dst_ptr.data_ptr<int64_t>(), n_dst, (int)heads, chead,
-                gw.data_ptr<float>());
-        }
+        qk::launch_segment_wsum_bwd_w(c.stream, c.elem, grad_out.data_ptr(),
+                                      c.feat.data_ptr(), c.src_ptr(),
+                                      c.dst_ptr_ptr(), c.n_dst, (int)heads,
+                                      chead, gw.data_ptr<float>());
     }
     return {gx, gw};
 }
@@ -1393,52 +1393,47 @@ std::tuple<torch::Tensor, torch::Tensor> segment_wsum_backward(
 // Numerically-stable segment softmax over [E, H] (dst_ptr segments).
 torch::Tensor segment_softmax(torch::Tensor a, torch::Tensor dst_ptr,
                               int64_t heads) {
-    TORCH_CHECK(a.is_cuda() && a.dtype() == torch::kFloat32 && a.dim() == 2 &&
-                a.size(1) == heads);
-    a = a.contiguous();
-    dst_ptr = dst_ptr.contiguous();
-    int64_t n_dst = dst_ptr.numel() - 1;
-    auto out = torch::empty_like(a);
-    qk::launch_segment_softmax_fwd(current_stream(), a.data_ptr<float>(),
-                                   dst_ptr.data_ptr<int64_t>(), n_dst,
-                                   (int)heads, out.data_ptr<float>());
+    SegmentCall c("segment_softmax", "a", a, true, nullptr, &dst_ptr);
+    TORCH_CHECK(c.dim == heads, "segment_softmax: a must be [n_edges, heads]");
+    auto out = torch::empty_like(c.feat);
+    qk::launch_segment_softmax_fwd(c.stream, c.feat.data_ptr<float>(),
+                                   c.dst_ptr_ptr(), c.n_dst, (int)heads,
+                                   out.data_ptr<float>());
     return out;
 }
 
 torch::Tensor segment_softmax_backward(torch::Tensor grad_out,
                                        torch::Tensor out,
                                        torch::Tensor dst_ptr, int64_t heads) {
-    grad_out = grad_out.contiguous();
-    out = out.contiguous();
-    dst_ptr = dst_ptr.contiguous();
-    int64_t n_dst = dst_ptr.numel() - 1;
-    auto ga = torch::empty_like(out);
-    qk::launch_segment_softmax_bwd(current_stream(),
-                                   grad_out.data_ptr<float>(),
-                                   out.data_ptr<float>(),
-                                   dst_ptr.data_ptr<int64_t>(), n_dst,
-                                   (int)heads, ga.data_ptr<float>());
+    SegmentCall c("segment_softmax_backward", "out", out, true, nullptr,
+                  &dst_ptr);
+    TORCH_CHECK(c.dim == heads,
+                "segment_softmax_backward: out must be [n_edges, heads]");
+    grad_out = c.arg("grad_out", grad_out, torch::kFloat32, c.feat.sizes());
+    auto ga = torch::empty_like(c.feat);
+    qk::launch_segment_softmax_bwd(c.stream, grad_out.data_ptr<float>(),
+                                   c.feat.data_ptr<float>(), c.dst_ptr_ptr(),
+                                   c.n_dst, (int)heads, ga.data_ptr<float>());
     return ga;
 }
 
 // Fused GAT attention coefficients (gather + add + leaky_relu + segment
 // softmax in one pass; no [E,H] intermediates materialized by torch).
+// asrc [n_src, heads]; adst has a row per dst segment.
 torch::Tensor gat_alpha(torch::Tensor asrc, torch::Tensor adst,
                         torch::Tensor src, torch::Tensor dst_ptr,
                         int64_t heads, double slope, int64_t n_edges) {
-    TORCH_CHECK(asrc.is_cuda() && asrc.dtype() == torch::kFloat32 &&
-                adst.dtype() == torch::kFloat32 &&
-                asrc.size(1) == heads && adst.size(1) == heads);
-    asrc = asrc.contiguous();
-    adst = adst.contiguous();
-    src = src.contiguous();
-    dst_ptr = dst_ptr.contiguous();
-    int64_t n_dst = dst_ptr.numel() - 1;
-    auto alpha = torch::empty({n_edges, heads}, asrc.options());
-    qk::launch_gat_alpha_fwd(current_stream(), asrc.data_ptr<float>(),
-                             adst.data_ptr<float>(),
-                             src.data_ptr<int64_t>(),
-                             dst_ptr.data_ptr<int64_t>(), n_dst, (int)heads,
+    SegmentCall c("gat_alpha", "asrc", asrc, true, &src, &dst_ptr);
+    TORCH_CHECK(c.dim == heads, "gat_alpha: asrc must be [n_src, heads]");
+    TORCH_CHECK(n_edges == c.src.numel(), "gat_alpha: n_edges ", n_edges,
+                " != src.numel() ", c.src.numel());
+    TORCH_CHECK(adst.dim() == 2 && adst.size(0) >= c.n_dst,
+                "gat_alpha: adst needs a row per dst_ptr segment");
+    adst = c.arg("adst", adst, torch::kFloat32, {adst.size(0), heads});
+    auto alpha = torch::empty({n_edges, heads}, c.feat.options());
+    qk::launch_gat_alpha_fwd(c.stream, c.feat.data_ptr<float>(),
+                             adst.data_ptr<float>(), c.src_ptr(),
+                             c.dst_ptr_ptr(), c.n_dst, (int)heads,
                              (float)slope, alpha.data_ptr<float>());
     return alpha;
 }
@@ -1447,20 +1442,21 @@ std::tuple<torch::Tensor, torch::Tensor> gat_alpha_backward(
     torch::Tensor grad_alpha, torch::Tensor alpha, torch::Tensor asrc,
     torch::Tensor adst, torch::Tensor src, torch::Tensor dst_ptr,
     int64_t heads, double slope) {
-    grad_alpha = grad_alpha.contiguous();
-    alpha = alpha.contiguous();
-    asrc = asrc.contiguous();
-    adst = adst.contiguous();
-    src = src.contiguous();
-    dst_ptr = dst_ptr.contiguous();
-    int64_t n_dst = dst_ptr.numel() - 1;
-    auto g_asrc = torch::zeros_like(asrc);
+    SegmentCall c("gat_alpha_backward", "asrc", asrc, true, &src, &dst_ptr);
+    TORCH_CHECK(c.dim == heads,
+                "gat_alpha_backward: asrc must be [n_src, heads]");
+    TORCH_CHECK(adst.dim() == 2 && adst.size(0) >= c.n_dst,
+                "gat_alpha_backward: adst needs a row per dst_ptr segment");
+    adst = c.arg("adst", adst, torch::kFloat32, {adst.size(0), heads});
+    alpha = c.arg("alpha", alpha, torch::kFloat32, {c.src.numel(), heads});
+    grad_alpha = c.arg("grad_alpha", grad_alpha, torch::kFloat32,
+                       alpha.sizes());
+    auto g_asrc = torch::zeros_like(c.feat);
     auto g_adst = torch::zeros_like(adst);
     qk::launch_gat_alpha_bwd(
-        current_stream(), grad_alpha.data_ptr<float>(),
-        alpha.data_ptr<float>(), asrc.data_ptr<float>(),
-        adst.data_ptr<float>(), src.data_ptr<int64_t>(),
-        dst_ptr.data_ptr<int64_t>(), n_dst, (int)heads, (float)slope,
+        c.stream, grad_alpha.data_ptr<float>(), alpha.data_ptr<float>(),
+        c.feat.data_ptr<float>(), adst.data_ptr<float>(), c.src_ptr(),
+        c.dst_ptr_ptr(), c.n_dst, (int)heads, (float)slope,
         g_asrc.data_ptr<float>(), g_adst.data_ptr<float>());
     return {g_asrc, g_adst};
 }
@@ -1494,31 +1490,22 @@ torch::Tensor tall_gemm(torch::Tensor a, torch::Tensor b_kmajor,
     return c;
 }
 
-// Fused GAT attention dots (see segment_kernels.hip).
+// Fused GAT attention dots (see segment_kernels.hip).  h [n, heads*C];
+// the attention vectors hold heads*C fp32 values (logits are fp32).
 std::tuple<torch::Tensor, torch::Tensor> gat_dots(torch::Tensor h,
                                                   torch::Tensor att_src,
                                                   torch::Tensor att_dst,
                                                   int64_t n_dst,
                                                   int64_t heads) {
-    TORCH_CHECK(h.is_cuda() && h.dim() == 2 &&
-                (h.dtype() == torch::kFloat32 ||
-                 h.dtype() == torch::kBFloat16));
-    TORCH_CHECK(att_src.dtype() == torch::kFloat32 &&
-                att_dst.dtype() == torch::kFloat32,
-                "attention vectors stay fp32 (logits are fp32)");
-    h = h.contiguous();
-    att_src = att_src.contiguous();
-    att_dst = att_dst.contiguous();
-    const int64_t n = h.size(0);
-    const int chead = (int)(h.size(1) / heads);
-    TORCH_CHECK((int64_t)chead * heads == h.size(1), "dim % heads != 0");
-    TORCH_CHECK(att_src.numel() == h.size(1) &&
-                att_dst.numel() == h.size(1));
-    auto fopts = h.options().dtype(torch::kFloat32);
+    SegmentCall c("gat_dots", "h", h, false, nullptr, nullptr);
+    const int chead = c.chead(heads);
+    att_src = c.arg("att_src", att_src.reshape(-1), torch::kFloat32, {c.dim});
+    att_dst = c.arg("att_dst", att_dst.reshape(-1), torch::kFloat32, {c.dim});
+    const int64_t n = c.feat.size(0);
+    auto fopts = c.feat.options().dtype(torch::kFloat32);
     auto asrc = torch::empty({n, heads}, fopts);
     auto adst = torch::empty({n_dst, heads}, fopts);
-    qk::launch_gat_dots_fwd(current_stream(), h.data_ptr(),
-                            h.dtype() == torch::kBFloat16,
+    qk::launch_gat_dots_fwd(c.stream, c.elem, c.feat.data_ptr(),
                             att_src.data_ptr<float>(),
                             att_dst.data_ptr<float>(), n, n_dst, (int)heads,
                             chead, asrc.data_ptr<float>(),
@@ -1529,22 +1516,25 @@ std::tuple<torch::Tensor, torch::Tensor> gat_dots(torch::Tensor h,
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> gat_dots_backward(
     torch::Tensor h, torch::Tensor att_src, torch::Tensor att_dst,
     torch::Tensor g_asrc, torch::Tensor g_adst, int64_t heads) {
-    h = h.contiguous();
-    att_src = att_src.contiguous();
-    att_dst = att_dst.contiguous();
-    g_asrc = g_asrc.contiguous();
-    g_adst = g_adst.contiguous();
-    const int64_t n = h.size(0), n_dst = g_adst.size(0);
-    const int chead = (int)(h.size(1) / heads);
-    auto g_h = torch::empty_like(h);
-    auto g_as = torch::zeros_like(att_src);
-    auto g_ad = torch::zeros_like(att_dst);
+    SegmentCall c("gat_dots_backward", "h", h, false, nullptr, nullptr);
+    const int chead = c.chead(heads);
+    auto as = c.arg("att_src", att_src.reshape(-1), torch::kFloat32, {c.dim});
+    auto ad = c.arg("att_dst", att_dst.reshape(-1), torch::kFloat32, {c.dim});
+    const int64_t n = c.feat.size(0);
+    TORCH_CHECK(g_adst.dim() == 2 && g_adst.size(0) <= n,
+                "gat_dots_backward: g_adst has more rows than h");
+    const int64_t n_dst = g_adst.size(0);
+    g_asrc = c.arg("g_asrc", g_asrc, torch::kFloat32, {n, heads});
+    g_adst = c.arg("g_adst", g_adst, torch::kFloat32, {n_dst, heads});
+    auto g_h = torch::empty_like(c.feat);
+    // attention gradients come back in the shape the vectors came in
+    auto g_as = torch::zeros(att_src.sizes(), as.options());
+    auto g_ad = torch::zeros(att_dst.sizes(), ad.options());
     qk::launch_gat_dots_bwd(
-        current_stream(), h.data_ptr(), h.dtype() == torch::kBFloat16,
-        att_src.data_ptr<float>(), att_dst.data_ptr<float>(),
-        g_asrc.data_ptr<float>(), g_adst.data_ptr<float>(), n, n_dst,
-        (int)heads, chead, g_h.data_ptr(), g_as.data_ptr<float>(),
-        g_ad.data_ptr<float>());
+        c.stream, c.elem, c.feat.data_ptr(), as.data_ptr<float>(),
+        ad.data_ptr<float>(), g_asrc.data_ptr<float>(),
+        g_adst.data_ptr<float>(), n, n_dst, (int)heads, chead,
+        g_h.data_ptr(), g_as.data_ptr<float>(), g_ad.data_ptr<float>());
     return {g_h, g_as, g_ad};
 }
 

@@ -1,9 +1,20 @@
 // Common declarations shared by the HIP kernel TUs and the torch-binding TU.
 //
-// Design: kernel TUs (sample_kernels.hip, reindex_kernels.hip,
-// gather_kernels.hip) include only <hip/hip_runtime.h> and expose C-ABI
-// launchers taking raw pointers + a hipStream_t.  module.cpp owns all
-// torch::Tensor plumbing and memory allocation (torch caching allocator).
+// Design: the kernel TUs include only HIP headers and expose C-ABI
+// launchers taking raw pointers + a hipStream_t; a launcher also owns the
+// checks that guard its kernels' layout assumptions (std::runtime_error).
+// module.cpp owns all torch::Tensor plumbing, argument validation and
+// memory allocation (torch caching allocator).
+//
+// Kernel files, in the order of the sections below:
+//   sample_kernels.hip   neighbour sampling, scans, access probabilities
+//   reindex_kernels.hip  hash-table frontier reindex
+//   gather_kernels.hip   sharded feature gather / scatter
+//   gemm_kernels.hip     tall-M GEMM
+//   wgrad_kernels.hip    tall-skinny split-K weight gradient
+//   segment_kernels.hip  message passing over dst-sorted edges: segment
+//                        mean, weighted segment sum, segment softmax, GAT
+//                        attention coefficients and dots
 //
 // Capability parity map (reference: quiver-team/torch-quiver):
 //   sample_kernels.hip  ~ srcs/cpp/include/quiver/cuda_random.cu.hpp +
@@ -144,20 +155,6 @@ void launch_gather(hipStream_t s, const GatherSpec& spec,
 void launch_scatter(hipStream_t s, const GatherSpec& spec,
                     const int64_t* indices, int64_t n, const char* src);
 
-// Fused GAT attention dots: asrc[n,h] = <h[n,h,:], att_src[h,:]>, adst
-// over the first n_dst rows (prefix convention); backward also emits
-// g_h and the (tiny) att gradients via per-block LDS accumulation.
-// h (and g_h) may be fp32 or bf16 (h_bf16); logits/att stay fp32.
-void launch_gat_dots_fwd(hipStream_t s, const void* h, bool h_bf16,
-                         const float* att_src, const float* att_dst,
-                         int64_t n, int64_t n_dst, int heads, int chead,
-                         float* asrc, float* adst);
-void launch_gat_dots_bwd(hipStream_t s, const void* h, bool h_bf16,
-                         const float* att_src, const float* att_dst,
-                         const float* g_asrc, const float* g_adst,
-                         int64_t n, int64_t n_dst, int heads, int chead,
-                         void* g_h, float* g_att_src, float* g_att_dst);
-
 // ---------- tall-M GEMM (gemm_kernels.hip) -------------------------------
 
 // C[M×N] = A[M×K] @ B[K×N] (+ bias[N]) with M huge, K/N <= ~1024 and B
@@ -181,23 +178,24 @@ void launch_wgrad(hipStream_t s, const float* A, const float* B, float* C,
                   float* bias_grad, int64_t K, int M, int N,
                   const WgradPlan& plan, float* ws);
 
-// ---------- fused message-passing aggregation (segment_kernels.hip) ------
+// ---------- message passing over dst-sorted edges (segment_kernels.hip) ---
+//
+// Edges are grouped by destination: segment d is [dst_ptr[d], dst_ptr[d+1]).
+// Feature-row buffers (const void* / void*) hold fp32 or bf16 elements as
+// named by the Elem tag; accumulation is fp32 either way, weights, logits
+// and attention vectors are always fp32.  bf16 rows need an even dim.
 
-// out[d] = mean over edges e in [dst_ptr[d], dst_ptr[d+1]) of x[src[e]]
-void launch_segment_mean_fwd(hipStream_t s, const float* x,
+enum class Elem { f32, bf16 };
+
+// out[d] = mean over the edges e of segment d of x[src[e]]
+void launch_segment_mean_fwd(hipStream_t s, Elem et, const void* x,
                              const int64_t* src, const int64_t* dst_ptr,
-                             int64_t n_dst, int64_t dim, float* out);
-// bf16 variants: bf16 rows, fp32 accumulation, packed-bf16 atomics (bwd)
-void launch_segment_mean_fwd_bf16(hipStream_t s, const void* x,
-                                  const int64_t* src, const int64_t* dst_ptr,
-                                  int64_t n_dst, int64_t dim, void* out);
-void launch_segment_mean_bwd_bf16(hipStream_t s, const void* grad_out,
-                                  const int64_t* src, const int64_t* dst_ptr,
-                                  int64_t n_dst, int64_t dim, void* grad_x);
-// grad_x[src[e]] += grad_out[d] / deg(d)   (grad_x pre-zeroed)
-void launch_segment_mean_bwd(hipStream_t s, const float* grad_out,
+                             int64_t n_dst, int64_t dim, void* out);
+// grad_x[src[e]] += grad_out[d] / deg(d)   (grad_x pre-filled; bf16 uses
+// packed-bf16 atomics)
+void launch_segment_mean_bwd(hipStream_t s, Elem et, const void* grad_out,
                              const int64_t* src, const int64_t* dst_ptr,
-                             int64_t n_dst, int64_t dim, float* grad_x);
+                             int64_t n_dst, int64_t dim, void* grad_x);
 // lanes per dst segment the kernels above use for a row of `dim` channels,
 // and how many gathered rows the forward keeps in flight per segment
 int segment_mean_lanes(int64_t dim, bool bf16);
@@ -209,31 +207,20 @@ void launch_prefix_fill(hipStream_t s, const void* head, int64_t head_bytes,
                         int64_t total_bytes, void* out);
 
 // Weighted segment sum (GAT attention aggregation), x [n_src, H*C],
-// w [n_edges, H] (per-edge per-head attention):
+// w [n_edges, H] (per-edge per-head attention); C % 4 == 0 when H > 1:
 //   out[d, h*C+c] = sum_{e in segment(d)} w[e,h] * x[src[e], h*C+c]
-void launch_segment_wsum_fwd_bf16(hipStream_t s, const void* x,
-                                  const float* w, const int64_t* src,
-                                  const int64_t* dst_ptr, int64_t n_dst,
-                                  int heads, int chead, void* out);
-void launch_segment_wsum_bwd_x_bf16(hipStream_t s, const void* grad_out,
-                                    const float* w, const int64_t* src,
-                                    const int64_t* dst_ptr, int64_t n_dst,
-                                    int heads, int chead, void* grad_x);
-void launch_segment_wsum_bwd_w_bf16(hipStream_t s, const void* grad_out,
-                                    const void* x, const int64_t* src,
-                                    const int64_t* dst_ptr, int64_t n_dst,
-                                    int heads, int chead, float* grad_w);
-void launch_segment_wsum_fwd(hipStream_t s, const float* x, const float* w,
-                             const int64_t* src, const int64_t* dst_ptr,
-                             int64_t n_dst, int heads, int chead, float* out);
+void launch_segment_wsum_fwd(hipStream_t s, Elem et, const void* x,
+                             const float* w, const int64_t* src,
+                             const int64_t* dst_ptr, int64_t n_dst, int heads,
+                             int chead, void* out);
 // grad_x[src[e], h*C+c] += w[e,h] * grad_out[d, h*C+c]  (pre-zeroed)
-void launch_segment_wsum_bwd_x(hipStream_t s, const float* grad_out,
+void launch_segment_wsum_bwd_x(hipStream_t s, Elem et, const void* grad_out,
                                const float* w, const int64_t* src,
                                const int64_t* dst_ptr, int64_t n_dst,
-                               int heads, int chead, float* grad_x);
+                               int heads, int chead, void* grad_x);
 // grad_w[e,h] = sum_c grad_out[d, h*C+c] * x[src[e], h*C+c]
-void launch_segment_wsum_bwd_w(hipStream_t s, const float* grad_out,
-                               const float* x, const int64_t* src,
+void launch_segment_wsum_bwd_w(hipStream_t s, Elem et, const void* grad_out,
+                               const void* x, const int64_t* src,
                                const int64_t* dst_ptr, int64_t n_dst,
                                int heads, int chead, float* grad_w);
 
@@ -262,5 +249,19 @@ void launch_gat_alpha_bwd(hipStream_t s, const float* grad_alpha,
                           const float* adst, const int64_t* src,
                           const int64_t* dst_ptr, int64_t n_dst, int heads,
                           float slope, float* g_asrc, float* g_adst);
+
+// Fused GAT attention dots: asrc[n,h] = <h[n,h,:], att_src[h,:]>, adst
+// over the first n_dst rows (prefix convention); backward also emits
+// g_h and the (tiny) att gradients via per-block LDS accumulation
+// (heads*chead <= 4096).  h and g_h are feature rows; chead % 4 == 0.
+void launch_gat_dots_fwd(hipStream_t s, Elem et, const void* h,
+                         const float* att_src, const float* att_dst,
+                         int64_t n, int64_t n_dst, int heads, int chead,
+                         float* asrc, float* adst);
+void launch_gat_dots_bwd(hipStream_t s, Elem et, const void* h,
+                         const float* att_src, const float* att_dst,
+                         const float* g_asrc, const float* g_adst,
+                         int64_t n, int64_t n_dst, int heads, int chead,
+                         void* g_h, float* g_att_src, float* g_att_dst);
 
 }  // namespace qk

@@ -381,59 +381,36 @@ segment_wsum_fwd_kernel(const XT* __restrict__ x,
     }
 }
 
+// Scatter of the weighted gradient: lanes own words lane, lane + SUB, ...
+// of the row (one channel in fp32, a channel pair in bf16 so the scatter
+// uses the packed-bf16 atomic).  A word lies within one head: bf16 rows
+// have an even dim, and chead % 4 == 0 when heads > 1 (both guarded by
+// the launcher).
+template <typename T>
 __global__ void __launch_bounds__(BLOCK)
-segment_wsum_bwd_x_kernel(const float* __restrict__ grad_out,
+segment_wsum_bwd_x_kernel(const T* __restrict__ grad_out,
                           const float* __restrict__ w,
                           const int64_t* __restrict__ src,
                           const int64_t* __restrict__ dst_ptr, int64_t n_dst,
-                          int heads, int chead, float* __restrict__ grad_x) {
+                          int heads, int chead, T* __restrict__ grad_x) {
+    using io = atomio<T>;
+    using word_t = typename io::word_t;
     const int64_t dim = (int64_t)heads * chead;
+    const int64_t words = dim / io::EPW;
     const int sub_id = threadIdx.x / SUB;
     const int lane = threadIdx.x % SUB;
     int64_t d = (int64_t)blockIdx.x * ROWS_PER_BLOCK + sub_id;
     const int64_t stride = (int64_t)gridDim.x * ROWS_PER_BLOCK;
     for (; d < n_dst; d += stride) {
         const int64_t beg = dst_ptr[d], end = dst_ptr[d + 1];
-        const float* orow = grad_out + d * dim;
+        const word_t* orow =
+            reinterpret_cast<const word_t*>(grad_out + d * dim);
         for (int64_t e = beg; e < end; ++e) {
-            float* grow = grad_x + src[e] * dim;
+            word_t* grow = reinterpret_cast<word_t*>(grad_x + src[e] * dim);
             const float* wrow = w + e * heads;
-            for (int64_t c = lane; c < dim; c += SUB)
-                atomicAdd(&grow[c], wrow[c / chead] * orow[c]);
-        }
-    }
-}
-
-// bf16 variant: grad_out and grad_x are bf16; weights fp32.  Lanes own
-// CHANNEL PAIRS so the scatter uses the packed-bf16 global atomic
-// (dim % 2 == 0 guarded by the launcher; chead % 2 == 0 keeps a pair
-// within one head when heads > 1 -- implied by the chead % 4 guard).
-__global__ void __launch_bounds__(BLOCK)
-segment_wsum_bwd_x_bf16_kernel(const __hip_bfloat16* __restrict__ grad_out,
-                               const float* __restrict__ w,
-                               const int64_t* __restrict__ src,
-                               const int64_t* __restrict__ dst_ptr,
-                               int64_t n_dst, int heads, int chead,
-                               __hip_bfloat16* __restrict__ grad_x) {
-    const int64_t dim = (int64_t)heads * chead;
-    const int sub_id = threadIdx.x / SUB;
-    const int lane = threadIdx.x % SUB;
-    int64_t d = (int64_t)blockIdx.x * ROWS_PER_BLOCK + sub_id;
-    const int64_t stride = (int64_t)gridDim.x * ROWS_PER_BLOCK;
-    for (; d < n_dst; d += stride) {
-        const int64_t beg = dst_ptr[d], end = dst_ptr[d + 1];
-        const __hip_bfloat16* orow = grad_out + d * dim;
-        for (int64_t e = beg; e < end; ++e) {
-            __hip_bfloat16* grow = grad_x + src[e] * dim;
-            const float* wrow = w + e * heads;
-            for (int64_t c = 2 * lane; c + 1 < dim; c += 2 * SUB) {
-                const float we = wrow[c / chead];
-                const float2 g = __bfloat1622float2(
-                    *reinterpret_cast<const __hip_bfloat162*>(&orow[c]));
-                unsafeAtomicAdd(
-                    reinterpret_cast<__hip_bfloat162*>(&grow[c]),
-                    __float22bfloat162_rn(float2{we * g.x, we * g.y}));
-            }
+            for (int64_t k = lane; k < words; k += SUB)
+                io::add(grow + k,
+                        io::scale(orow[k], wrow[(k * io::EPW) / chead]));
         }
     }
 }
@@ -707,11 +684,44 @@ inline int grid_for(int64_t work, int per_block) {
     return (int)blocks;
 }
 
+// ---- launch layer ---------------------------------------------------------
+// Runs f with a tag whose ::type is the element type named by `et`, unless
+// there are no rows to work on, and reports a failed launch.  Every
+// launcher with dtype-dependent buffers goes through it.
+template <typename T> struct elem_tag { using type = T; };
+template <typename F> void launch_for(Elem et, int64_t rows, F&& f) {
+    if (rows == 0) return;
+    if (et == Elem::bf16) f(elem_tag<__hip_bfloat16>{});
+    else f(elem_tag<float>{});
+    QK_CHECK_HIP(hipGetLastError());
+}
+
+// Layout assumptions of the kernels, checked once per launch.
+void check_rows(const char* op, Elem et, int64_t dim) {
+    // bf16 rows move as 4-byte channel pairs
+    if (et == Elem::bf16 && dim % 2 != 0)
+        throw std::runtime_error(std::string(op) +
+                                 ": bf16 rows need an even feature dim");
+}
+void check_wsum(const char* op, Elem et, int heads, int chead) {
+    check_rows(op, et, (int64_t)heads * chead);
+    // heads == 1: the whole dim is one head, a vector chunk cannot
+    // straddle a head boundary regardless of chead
+    if (heads > 1 && chead % VPL != 0)
+        throw std::runtime_error(
+            std::string(op) + ": per-head channels must be a multiple of 4 "
+            "so vector chunks stay within one head");
+}
+void check_dots(int chead) {
+    if (chead % 4 != 0)
+        throw std::runtime_error("gat_dots: chead must be a multiple of 4");
+}
+
 }  // namespace
 
 // instantiate the lane-group width picked by lanes_for()
-#define QK_MEAN_DISPATCH(KERNEL, T, lanes, ...)                              \
-    switch (lanes) {                                                         \
+#define QK_MEAN_DISPATCH(KERNEL, T, ...)                                     \
+    switch (lanes_for(dim, rowio<T>::VPL)) {                                 \
     case 1: KERNEL<T, 1><<<grid_for(n_dst, BLOCK / 1), BLOCK, 0, s>>>(__VA_ARGS__); break;   \
     case 2: KERNEL<T, 2><<<grid_for(n_dst, BLOCK / 2), BLOCK, 0, s>>>(__VA_ARGS__); break;   \
     case 4: KERNEL<T, 4><<<grid_for(n_dst, BLOCK / 4), BLOCK, 0, s>>>(__VA_ARGS__); break;   \
@@ -728,45 +738,26 @@ int segment_mean_lanes(int64_t dim, bool bf16) {
 
 int segment_mean_rows_in_flight() { return MEAN_U; }
 
-void launch_segment_mean_fwd(hipStream_t s, const float* x,
+void launch_segment_mean_fwd(hipStream_t s, Elem et, const void* x,
                              const int64_t* src, const int64_t* dst_ptr,
-                             int64_t n_dst, int64_t dim, float* out) {
-    if (n_dst == 0) return;
-    QK_MEAN_DISPATCH(segment_mean_fwd_kernel, float,
-                     segment_mean_lanes(dim, false), x, src, dst_ptr, n_dst,
-                     dim, out);
-    QK_CHECK_HIP(hipGetLastError());
+                             int64_t n_dst, int64_t dim, void* out) {
+    check_rows("segment_mean", et, dim);
+    launch_for(et, n_dst, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        QK_MEAN_DISPATCH(segment_mean_fwd_kernel, T, (const T*)x, src,
+                         dst_ptr, n_dst, dim, (T*)out);
+    });
 }
 
-void launch_segment_mean_bwd(hipStream_t s, const float* grad_out,
+void launch_segment_mean_bwd(hipStream_t s, Elem et, const void* grad_out,
                              const int64_t* src, const int64_t* dst_ptr,
-                             int64_t n_dst, int64_t dim, float* grad_x) {
-    if (n_dst == 0) return;
-    QK_MEAN_DISPATCH(segment_mean_bwd_kernel, float,
-                     segment_mean_lanes(dim, false), grad_out, src, dst_ptr,
-                     n_dst, dim, grad_x);
-    QK_CHECK_HIP(hipGetLastError());
-}
-
-void launch_segment_mean_fwd_bf16(hipStream_t s, const void* x,
-                                  const int64_t* src, const int64_t* dst_ptr,
-                                  int64_t n_dst, int64_t dim, void* out) {
-    if (n_dst == 0) return;
-    QK_MEAN_DISPATCH(segment_mean_fwd_kernel, __hip_bfloat16,
-                     segment_mean_lanes(dim, true), (const __hip_bfloat16*)x,
-                     src, dst_ptr, n_dst, dim, (__hip_bfloat16*)out);
-    QK_CHECK_HIP(hipGetLastError());
-}
-
-void launch_segment_mean_bwd_bf16(hipStream_t s, const void* grad_out,
-                                  const int64_t* src, const int64_t* dst_ptr,
-                                  int64_t n_dst, int64_t dim, void* grad_x) {
-    if (n_dst == 0) return;
-    QK_MEAN_DISPATCH(segment_mean_bwd_kernel, __hip_bfloat16,
-                     segment_mean_lanes(dim, true),
-                     (const __hip_bfloat16*)grad_out, src, dst_ptr, n_dst,
-                     dim, (__hip_bfloat16*)grad_x);
-    QK_CHECK_HIP(hipGetLastError());
+                             int64_t n_dst, int64_t dim, void* grad_x) {
+    check_rows("segment_mean", et, dim);
+    launch_for(et, n_dst, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        QK_MEAN_DISPATCH(segment_mean_bwd_kernel, T, (const T*)grad_out, src,
+                         dst_ptr, n_dst, dim, (T*)grad_x);
+    });
 }
 
 #undef QK_MEAN_DISPATCH
@@ -786,87 +777,45 @@ void launch_prefix_fill(hipStream_t s, const void* head, int64_t head_bytes,
     QK_CHECK_HIP(hipGetLastError());
 }
 
-static void check_chead(int heads, int chead) {
-    // heads == 1: the whole dim is one head, a vector chunk cannot
-    // straddle a head boundary regardless of chead
-    if (heads > 1 && chead % VPL != 0)
-        throw std::runtime_error(
-            "segment_wsum: per-head channels must be a multiple of 4 "
-            "so vector chunks stay within one head");
+void launch_segment_wsum_fwd(hipStream_t s, Elem et, const void* x,
+                             const float* w, const int64_t* src,
+                             const int64_t* dst_ptr, int64_t n_dst, int heads,
+                             int chead, void* out) {
+    check_wsum("segment_wsum", et, heads, chead);
+    launch_for(et, n_dst, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        segment_wsum_fwd_kernel<T>
+            <<<grid_for(n_dst, ROWS_PER_BLOCK), BLOCK, 0, s>>>(
+                (const T*)x, w, src, dst_ptr, n_dst, heads, chead, (T*)out);
+    });
 }
 
-void launch_segment_wsum_fwd(hipStream_t s, const float* x, const float* w,
-                             const int64_t* src, const int64_t* dst_ptr,
-                             int64_t n_dst, int heads, int chead, float* out) {
-    if (n_dst == 0) return;
-    check_chead(heads, chead);
-    segment_wsum_fwd_kernel<float>
-        <<<grid_for(n_dst, ROWS_PER_BLOCK), BLOCK, 0, s>>>(
-            x, w, src, dst_ptr, n_dst, heads, chead, out);
-    QK_CHECK_HIP(hipGetLastError());
-}
-
-void launch_segment_wsum_fwd_bf16(hipStream_t s, const void* x,
-                                  const float* w, const int64_t* src,
-                                  const int64_t* dst_ptr, int64_t n_dst,
-                                  int heads, int chead, void* out) {
-    if (n_dst == 0) return;
-    check_chead(heads, chead);
-    segment_wsum_fwd_kernel<__hip_bfloat16>
-        <<<grid_for(n_dst, ROWS_PER_BLOCK), BLOCK, 0, s>>>(
-            (const __hip_bfloat16*)x, w, src, dst_ptr, n_dst, heads, chead,
-            (__hip_bfloat16*)out);
-    QK_CHECK_HIP(hipGetLastError());
-}
-
-void launch_segment_wsum_bwd_x(hipStream_t s, const float* grad_out,
+void launch_segment_wsum_bwd_x(hipStream_t s, Elem et, const void* grad_out,
                                const float* w, const int64_t* src,
                                const int64_t* dst_ptr, int64_t n_dst,
-                               int heads, int chead, float* grad_x) {
-    if (n_dst == 0) return;
-    check_chead(heads, chead);
-    segment_wsum_bwd_x_kernel<<<grid_for(n_dst, ROWS_PER_BLOCK), BLOCK, 0,
-                                s>>>(grad_out, w, src, dst_ptr, n_dst, heads,
-                                     chead, grad_x);
-    QK_CHECK_HIP(hipGetLastError());
+                               int heads, int chead, void* grad_x) {
+    check_wsum("segment_wsum", et, heads, chead);
+    launch_for(et, n_dst, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        segment_wsum_bwd_x_kernel<T>
+            <<<grid_for(n_dst, ROWS_PER_BLOCK), BLOCK, 0, s>>>(
+                (const T*)grad_out, w, src, dst_ptr, n_dst, heads, chead,
+                (T*)grad_x);
+    });
 }
 
-void launch_segment_wsum_bwd_x_bf16(hipStream_t s, const void* grad_out,
-                                    const float* w, const int64_t* src,
-                                    const int64_t* dst_ptr, int64_t n_dst,
-                                    int heads, int chead, void* grad_x) {
-    if (n_dst == 0) return;
-    check_chead(heads, chead);
-    segment_wsum_bwd_x_bf16_kernel
-        <<<grid_for(n_dst, ROWS_PER_BLOCK), BLOCK, 0, s>>>(
-            (const __hip_bfloat16*)grad_out, w, src, dst_ptr, n_dst, heads,
-            chead, (__hip_bfloat16*)grad_x);
-    QK_CHECK_HIP(hipGetLastError());
-}
-
-void launch_segment_wsum_bwd_w(hipStream_t s, const float* grad_out,
-                               const float* x, const int64_t* src,
+void launch_segment_wsum_bwd_w(hipStream_t s, Elem et, const void* grad_out,
+                               const void* x, const int64_t* src,
                                const int64_t* dst_ptr, int64_t n_dst,
                                int heads, int chead, float* grad_w) {
-    if (n_dst == 0) return;
-    check_chead(heads, chead);
-    segment_wsum_bwd_w_kernel<float>
-        <<<grid_for(n_dst, ROWS_PER_BLOCK), BLOCK, 0, s>>>(
-            grad_out, x, src, dst_ptr, n_dst, heads, chead, grad_w);
-    QK_CHECK_HIP(hipGetLastError());
-}
-
-void launch_segment_wsum_bwd_w_bf16(hipStream_t s, const void* grad_out,
-                                    const void* x, const int64_t* src,
-                                    const int64_t* dst_ptr, int64_t n_dst,
-                                    int heads, int chead, float* grad_w) {
-    if (n_dst == 0) return;
-    check_chead(heads, chead);
-    segment_wsum_bwd_w_kernel<__hip_bfloat16>
-        <<<grid_for(n_dst, ROWS_PER_BLOCK), BLOCK, 0, s>>>(
-            (const __hip_bfloat16*)grad_out, (const __hip_bfloat16*)x, src,
-            dst_ptr, n_dst, heads, chead, grad_w);
-    QK_CHECK_HIP(hipGetLastError());
+    check_wsum("segment_wsum", et, heads, chead);
+    launch_for(et, n_dst, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        segment_wsum_bwd_w_kernel<T>
+            <<<grid_for(n_dst, ROWS_PER_BLOCK), BLOCK, 0, s>>>(
+                (const T*)grad_out, (const T*)x, src, dst_ptr, n_dst, heads,
+                chead, grad_w);
+    });
 }
 
 void launch_segment_softmax_fwd(hipStream_t s, const float* a,
@@ -910,50 +859,37 @@ void launch_gat_alpha_bwd(hipStream_t s, const float* grad_alpha,
     QK_CHECK_HIP(hipGetLastError());
 }
 
-
-void launch_gat_dots_fwd(hipStream_t s, const void* h, bool h_bf16,
+void launch_gat_dots_fwd(hipStream_t s, Elem et, const void* h,
                          const float* att_src, const float* att_dst,
                          int64_t n, int64_t n_dst, int heads, int chead,
                          float* asrc, float* adst) {
-    if (n == 0) return;
-    if (chead % 4 != 0)
-        throw std::runtime_error("gat_dots: chead must be a multiple of 4");
-    const int grid = grid_for(n * heads, BLOCK / DSUB);
-    if (h_bf16)
-        gat_dots_fwd_kernel<__hip_bfloat16><<<grid, BLOCK, 0, s>>>(
-            (const __hip_bfloat16*)h, att_src, att_dst, n, n_dst, heads,
-            chead, asrc, adst);
-    else
-        gat_dots_fwd_kernel<float><<<grid, BLOCK, 0, s>>>(
-            (const float*)h, att_src, att_dst, n, n_dst, heads, chead,
-            asrc, adst);
-    QK_CHECK_HIP(hipGetLastError());
+    check_dots(chead);
+    launch_for(et, n, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        gat_dots_fwd_kernel<T>
+            <<<grid_for(n * heads, BLOCK / DSUB), BLOCK, 0, s>>>(
+                (const T*)h, att_src, att_dst, n, n_dst, heads, chead, asrc,
+                adst);
+    });
 }
 
-void launch_gat_dots_bwd(hipStream_t s, const void* h, bool h_bf16,
+void launch_gat_dots_bwd(hipStream_t s, Elem et, const void* h,
                          const float* att_src, const float* att_dst,
                          const float* g_asrc, const float* g_adst,
                          int64_t n, int64_t n_dst, int heads, int chead,
                          void* g_h, float* g_att_src, float* g_att_dst) {
-    if (n == 0) return;
-    if (chead % 4 != 0)
-        throw std::runtime_error("gat_dots: chead must be a multiple of 4");
-    const int D = heads * chead;
-    if (D > 4096)
+    check_dots(chead);
+    // the kernel keeps two [heads*chead] fp32 accumulators in LDS
+    if ((int64_t)heads * chead > 4096)
         throw std::runtime_error("gat_dots: heads*chead too large for LDS");
-    const int grid = grid_for(n * heads, BLOCK / DSUB);
-    if (h_bf16)
-        gat_dots_bwd_kernel<__hip_bfloat16>
-            <<<grid, BLOCK, 2 * D * sizeof(float), s>>>(
-                (const __hip_bfloat16*)h, att_src, att_dst, g_asrc, g_adst,
-                n, n_dst, heads, chead, (__hip_bfloat16*)g_h, g_att_src,
-                g_att_dst);
-    else
-        gat_dots_bwd_kernel<float>
-            <<<grid, BLOCK, 2 * D * sizeof(float), s>>>(
-                (const float*)h, att_src, att_dst, g_asrc, g_adst, n,
-                n_dst, heads, chead, (float*)g_h, g_att_src, g_att_dst);
-    QK_CHECK_HIP(hipGetLastError());
+    const size_t lds = 2 * (size_t)heads * chead * sizeof(float);
+    launch_for(et, n, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        gat_dots_bwd_kernel<T>
+            <<<grid_for(n * heads, BLOCK / DSUB), BLOCK, lds, s>>>(
+                (const T*)h, att_src, att_dst, g_asrc, g_adst, n, n_dst,
+                heads, chead, (T*)g_h, g_att_src, g_att_dst);
+    });
 }
 
 }  // namespace qk

@@ -5,8 +5,10 @@ has no PyG, so the SAGE/GAT model families used by examples, serving and
 bench.py live here.  The layers follow PyG's bipartite convention: forward
 ((x_src, x_dst), edge_index, size) with edge_index[0] indexing x_src and
 edge_index[1] indexing x_dst — exactly what GraphSageSampler's adjs feed.
-Aggregations use index_add / scatter_reduce, which lower to native ROCm
-kernels.
+On GPU tensors with dst-sorted edges (the sampler's layout) aggregation and
+attention run on the fused HIP segment kernels (csrc/segment_kernels.hip)
+through the autograd functions below; other inputs take the plain torch
+index_add / scatter_reduce chain.
 """
 from typing import Tuple
 
@@ -149,26 +151,6 @@ class _GatAlpha(torch.autograd.Function):
         return g_asrc, g_adst, None, None, None, None, None
 
 
-class _SegmentSoftmax(torch.autograd.Function):
-    """Softmax over dst-sorted edge segments (csrc/segment_kernels.hip).
-    torch's scatter_reduce(amax) path lowers to ~120 rocprim sort kernels
-    per step on ROCm; this is two scalar kernels."""
-
-    @staticmethod
-    def forward(ctx, a, dst_ptr, heads):
-        out = _ext.segment_softmax(a, dst_ptr, heads)
-        ctx.save_for_backward(out, dst_ptr)
-        ctx.heads = heads
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        out, dst_ptr = ctx.saved_tensors
-        return (_ext.segment_softmax_backward(grad_out.contiguous(), out,
-                                              dst_ptr, ctx.heads),
-                None, None)
-
-
 class _QLinearFn(torch.autograd.Function):
     """Linear layer whose weight gradient uses the split-K HIP kernel
     (csrc/wgrad_kernels.hip).
@@ -266,6 +248,15 @@ def _dst_ptr_for(edge_index, n_dst):
     return ptr
 
 
+def _is_prefix(x_src, x_dst):
+    """x_dst is the leading rows of x_src, as a view (the bipartite prefix
+    convention: the models pass (x, x[:n_dst]))."""
+    return (x_dst.data_ptr() == x_src.data_ptr()
+            and x_dst.size(0) <= x_src.size(0)
+            and x_dst.stride() == x_src.stride()
+            and x_dst.size(1) == x_src.size(1))
+
+
 def _fused_mean_ok(x_src, dst, sorted_dst):
     return (sorted_dst and x_src.is_cuda and dst.numel() > 0
             and (x_src.dtype == torch.float32
@@ -273,20 +264,24 @@ def _fused_mean_ok(x_src, dst, sorted_dst):
                      and x_src.size(1) % 2 == 0)))
 
 
-def _mean_aggregate(x_src, src, dst, n_dst, sorted_dst=False, dst_ptr=None):
-    """Mean of x_src[src] grouped by dst.  Uses the fused HIP kernel when
-    the caller guarantees dst is sorted ascending (our sampler's layout)
-    on fp32 GPU tensors."""
-    if _fused_mean_ok(x_src, dst, sorted_dst):
-        if dst_ptr is None:
-            dst_ptr = _dst_ptr_from_sorted(dst, n_dst)
-        return _SegmentMeanAgg.apply(x_src, src, dst_ptr)
+def _mean_torch(x_src, src, dst, n_dst):
     agg = torch.zeros((n_dst, x_src.size(1)), dtype=x_src.dtype,
                       device=x_src.device)
     agg.index_add_(0, dst, x_src[src])
     deg = torch.zeros(n_dst, dtype=x_src.dtype, device=x_src.device)
     deg.index_add_(0, dst, torch.ones_like(dst, dtype=x_src.dtype))
     return agg / deg.clamp_(min=1).unsqueeze(-1)
+
+
+def _mean_aggregate(x_src, src, dst, n_dst, sorted_dst=False, dst_ptr=None):
+    """Mean of x_src[src] grouped by dst.  Uses the fused HIP kernel when
+    the caller guarantees dst is sorted ascending (our sampler's layout)
+    on fp32 or even-width bf16 GPU tensors."""
+    if not _fused_mean_ok(x_src, dst, sorted_dst):
+        return _mean_torch(x_src, src, dst, n_dst)
+    if dst_ptr is None:
+        dst_ptr = _dst_ptr_from_sorted(dst, n_dst)
+    return _SegmentMeanAgg.apply(x_src, src, dst_ptr)
 
 
 class SAGEConv(nn.Module):
@@ -315,25 +310,19 @@ class SAGEConv(nn.Module):
         src, dst = edge_index[0], edge_index[1]
         n_dst = x_dst.size(0) if size is None else int(size[1])
         # aggregate-then-project: segment mean on in_channels, one GEMM after
-        if _fused_mean_ok(x_src, dst, self.sorted_dst):
+        if not _fused_mean_ok(x_src, dst, self.sorted_dst):
+            agg = _mean_torch(x_src, src, dst, n_dst)
+        else:
             dst_ptr = _dst_ptr_for(edge_index, n_dst)
-            prefix = (x_dst.data_ptr() == x_src.data_ptr()
-                      and x_dst.size(0) <= x_src.size(0)
-                      and x_dst.stride() == x_src.stride()
-                      and x_dst.size(1) == x_src.size(1)
-                      and x_src.is_contiguous())
-            if (prefix and x_src.requires_grad and torch.is_grad_enabled()):
+            if (x_src.requires_grad and torch.is_grad_enabled()
+                    and x_src.is_contiguous() and _is_prefix(x_src, x_dst)):
                 # x feeds both paths: one function owns the whole input
                 # gradient (inputs without grad, e.g. layer 0, skip this
                 # and never run a backward)
                 agg, x_dst = _SegmentMeanPrefix.apply(x_src, src, dst_ptr,
                                                       x_dst.size(0))
             else:
-                agg = _mean_aggregate(x_src, src, dst, n_dst,
-                                      sorted_dst=True, dst_ptr=dst_ptr)
-        else:
-            agg = _mean_aggregate(x_src, src, dst, n_dst,
-                                  sorted_dst=self.sorted_dst)
+                agg = _SegmentMeanAgg.apply(x_src, src, dst_ptr)
         out = self.lin_l(agg)
         if (x_dst.is_cuda and x_dst.dtype == torch.float32
                 and x_dst.size(0) >= _WGRAD_MIN_K
@@ -388,16 +377,18 @@ class GATConv(nn.Module):
         # (scatter_reduce amax -> ~120 rocprim sort kernels) is far
         # slower than either.
         out_dtype = h2.dtype
-        native = (h2.is_cuda and self.sorted_dst and C % 4 == 0
+        # decided once: `segments` = dst-sorted edges on the GPU (the alpha
+        # kernel's layout), `native` = h additionally fits the dots/wsum
+        # kernels; dst_ptr is set exactly when a segment kernel may run
+        segments = self.sorted_dst and h2.is_cuda
+        native = (segments and C % 4 == 0
                   and h2.dtype in (torch.float32, torch.bfloat16))
-        if (h2.is_cuda and h2.dtype == torch.bfloat16 and self.sorted_dst
-                and not native):
+        if segments and not native and h2.dtype == torch.bfloat16:
             h2 = h2.float()
+        dst_ptr = (_dst_ptr_for(edge_index, n_dst)
+                   if segments and dst.numel() > 0 else None)
         h_src = h2.view(-1, H, C)
-        prefix = (x_dst.data_ptr() == x_src.data_ptr()
-                  and x_dst.size(0) <= x_src.size(0)
-                  and x_dst.stride() == x_src.stride()
-                  and x_dst.size(1) == x_src.size(1))
+        prefix = _is_prefix(x_src, x_dst)
         if prefix and native:
             # bipartite prefix convention (x_dst is x_src[:n_dst]) with
             # the fused dots kernel: one read of h for both logit sets
@@ -411,10 +402,7 @@ class GATConv(nn.Module):
                 h_dst = self.lin(x_dst).view(-1, H, C)
             alpha_src = (h_src * self.att_src).sum(-1)  # [N_src, H]
             alpha_dst = (h_dst * self.att_dst).sum(-1)  # [N_dst, H]
-        fused = (self.sorted_dst and alpha_src.is_cuda
-                 and alpha_src.dtype == torch.float32 and dst.numel() > 0)
-        if fused:
-            dst_ptr = _dst_ptr_for(edge_index, n_dst)
+        if dst_ptr is not None and alpha_src.dtype == torch.float32:
             alpha = _GatAlpha.apply(alpha_src, alpha_dst, src, dst_ptr, H,
                                     self.negative_slope, src.numel())
         else:
@@ -434,13 +422,9 @@ class GATConv(nn.Module):
         if self.training and self.dropout > 0:
             alpha = F.dropout(alpha, p=self.dropout)
 
-        if (self.sorted_dst and h_src.is_cuda and C % 4 == 0
-                and h_src.dtype in (torch.float32, torch.bfloat16)
-                and alpha.dtype == torch.float32
-                and dst.numel() > 0):
+        if (native and dst_ptr is not None
+                and alpha.dtype == torch.float32):
             # fused weighted segment sum over the dst-sorted edges
-            if not fused:
-                dst_ptr = _dst_ptr_for(edge_index, n_dst)
             out = _SegmentWSum.apply(h_src.reshape(-1, H * C), alpha, src,
                                      dst_ptr, H)
             out = out if self.concat else out.view(n_dst, H, C).mean(1)

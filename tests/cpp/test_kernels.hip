@@ -472,10 +472,10 @@ void test_segment_mean() {
     h2d(d_ptr, dst_ptr);
     h2d(d_go, go);
     QK_CHECK_HIP(hipMemset(d_gx, 0, x.size() * sizeof(float)));
-    qk::launch_segment_mean_fwd(nullptr, d_x, d_src, d_ptr, n_dst, dim,
-                                d_out);
-    qk::launch_segment_mean_bwd(nullptr, d_go, d_src, d_ptr, n_dst, dim,
-                                d_gx);
+    qk::launch_segment_mean_fwd(nullptr, qk::Elem::f32, d_x, d_src, d_ptr,
+                                n_dst, dim, d_out);
+    qk::launch_segment_mean_bwd(nullptr, qk::Elem::f32, d_go, d_src, d_ptr,
+                                n_dst, dim, d_gx);
     QK_CHECK_HIP(hipDeviceSynchronize());
     auto out = d2h(d_out, n_dst * dim);
     auto gx = d2h(d_gx, x.size());

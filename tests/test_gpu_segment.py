@@ -331,3 +331,83 @@ def test_gat_dots_bf16_matches_fp32():
     assert h16.grad.dtype == torch.bfloat16
     assert torch.isfinite(h16.grad.float()).all()
     assert a_s.grad is not None and torch.isfinite(a_s.grad).all()
+
+
+# ---- argument validation ---------------------------------------------------
+# Every case has zero segments (dst_ptr of one entry) and no edges, so the
+# launchers return before launching anything: a binding that lacks a check
+# fails with "did not raise" and never hands a bad pointer to a kernel.
+_H, _D = 2, 8
+
+
+def _z(*shape, dtype=torch.float32):
+    return torch.zeros(*shape, dtype=dtype, device="cuda")
+
+
+def _zero_segment_args():
+    return dict(x=_z(3, _D), go=_z(0, _D), w=_z(0, _H), asrc=_z(3, _H),
+                adst=_z(0, _H), alpha=_z(0, _H), h=_z(0, _D), att=_z(_D),
+                g_asrc=_z(0, _H), src=_z(0, dtype=torch.long),
+                ptr=_z(1, dtype=torch.long), heads=_H, n_edges=0)
+
+
+_CALLS = {
+    "segment_mean_gather": lambda a: _ext.segment_mean_gather(
+        a["x"], a["src"], a["ptr"]),
+    "segment_mean_gather_backward": lambda a:
+        _ext.segment_mean_gather_backward(a["go"], a["src"], a["ptr"], 3),
+    "segment_wsum": lambda a: _ext.segment_wsum(
+        a["x"], a["w"], a["src"], a["ptr"], a["heads"]),
+    "segment_wsum_backward": lambda a: _ext.segment_wsum_backward(
+        a["go"], a["x"], a["w"], a["src"], a["ptr"], a["heads"], True, True),
+    "segment_softmax": lambda a: _ext.segment_softmax(
+        a["alpha"], a["ptr"], a["heads"]),
+    "segment_softmax_backward": lambda a: _ext.segment_softmax_backward(
+        a["alpha"], a["alpha"], a["ptr"], a["heads"]),
+    "gat_alpha": lambda a: _ext.gat_alpha(
+        a["asrc"], a["adst"], a["src"], a["ptr"], a["heads"], 0.2,
+        a["n_edges"]),
+    "gat_alpha_backward": lambda a: _ext.gat_alpha_backward(
+        a["alpha"], a["alpha"], a["asrc"], a["adst"], a["src"], a["ptr"],
+        a["heads"], 0.2),
+    "gat_dots_backward": lambda a: _ext.gat_dots_backward(
+        a["h"], a["att"], a["att"], a["g_asrc"], a["g_asrc"], a["heads"]),
+}
+
+_BREAK = {
+    "src_on_cpu": lambda a: a.update(src=a["src"].cpu()),
+    "dst_ptr_on_cpu": lambda a: a.update(ptr=a["ptr"].cpu()),
+    "dst_ptr_empty": lambda a: a.update(ptr=a["ptr"][:0]),
+    "grad_out_dtype": lambda a: a.update(go=a["go"].bfloat16()),
+    "grad_out_rows": lambda a: a.update(go=_z(1, _D)),
+    # 6 channels over 4 heads
+    "dim_not_multiple_of_heads": lambda a: a.update(
+        x=_z(3, 6), go=_z(0, 6), w=_z(0, 4), h=_z(0, 6), att=_z(6),
+        g_asrc=_z(0, 4), heads=4),
+    "n_edges": lambda a: a.update(n_edges=5),
+}
+
+_WITH_SRC = ["segment_mean_gather", "segment_mean_gather_backward",
+             "segment_wsum", "segment_wsum_backward", "gat_alpha",
+             "gat_alpha_backward"]
+_WITH_DST_PTR = _WITH_SRC + ["segment_softmax", "segment_softmax_backward"]
+_BAD_ARGS = (
+    [(op, "src_on_cpu") for op in _WITH_SRC]
+    + [(op, "dst_ptr_on_cpu") for op in _WITH_DST_PTR]
+    # the ops that size an output by n_dst or compare against it
+    + [(op, "dst_ptr_empty") for op in _WITH_SRC[:3]]
+    + [("segment_wsum_backward", "grad_out_dtype"),
+       ("segment_mean_gather_backward", "grad_out_rows"),
+       ("segment_wsum_backward", "dim_not_multiple_of_heads"),
+       ("gat_dots_backward", "dim_not_multiple_of_heads"),
+       ("gat_alpha", "n_edges")])
+
+
+@pytest.mark.parametrize("op,fault", _BAD_ARGS,
+                         ids=[f"{op}-{fault}" for op, fault in _BAD_ARGS])
+def test_bad_arguments_raise(op, fault):
+    args = _zero_segment_args()
+    _CALLS[op](args)  # the well-formed call goes through
+    _BREAK[fault](args)
+    with pytest.raises(RuntimeError):
+        _CALLS[op](args)

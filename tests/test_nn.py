@@ -67,3 +67,13 @@ def test_models_forward_backward():
         loss.backward()
         grads = [p.grad for p in model.parameters() if p.grad is not None]
         assert len(grads) > 0
+
+
+def test_is_prefix():
+    from quiver.nn import _is_prefix
+    x = torch.randn(6, 4)
+    assert _is_prefix(x, x)
+    assert _is_prefix(x, x[:2])
+    assert not _is_prefix(x, x[:2].clone())
+    assert not _is_prefix(x, x[:, :2])
+    assert not _is_prefix(x[:2], x[:4])
