@@ -131,11 +131,11 @@ def gather(db, steps, skip=0):
     # the HBM tier runs on side streams that carry nothing but copy_rows;
     # the host tier shares its stream with the sampling chain
     side = {sid for sid, ks in busy.items()
-            if all("copy_rows_kernel" in n for n, _, _ in ks)}
+            if all("copy_rows_" in n for n, _, _ in ks)}
     host = [(s, e) for n, sid, s, e in rows
-            if "copy_rows_kernel" in n and sid not in side]
+            if "copy_rows_" in n and sid not in side]
     hbm = [(s, e) for n, sid, s, e in rows
-           if "copy_rows_kernel" in n and sid in side]
+           if "copy_rows_" in n and sid in side]
     t_from = host[skip][0] if skip else 0
     host = [iv for iv in host if iv[0] >= t_from]
     hbm = [iv for iv in hbm if iv[0] >= t_from]

@@ -69,6 +69,85 @@ copy_rows_kernel(GatherSpec spec, const int64_t* __restrict__ indices,
     }
 }
 
+// Host-tier gather with row reuse (GatherReuse, qk_common.h).  Same row
+// assignment and one row in flight per sub-group as copy_rows_kernel; the
+// only difference is where a row is read from.  The table entry is loaded
+// at one address by all lanes of the sub-group, so the choice of source
+// is uniform across it.
+template <typename VecT, int SUB>
+__global__ void __launch_bounds__(BLOCK)
+copy_rows_reuse_kernel(GatherSpec spec, GatherReuse ru,
+                       const int64_t* __restrict__ indices, int64_t n,
+                       char* __restrict__ out,
+                       const int64_t* __restrict__ n_dev,
+                       const int64_t* __restrict__ order, int64_t order_n) {
+    n = min(n, *n_dev);  // rows at or past *n_dev: no copy, no entry
+    const int sub_id = threadIdx.x / SUB;
+    const int lane = threadIdx.x % SUB;
+    const int rows_per_block = BLOCK / SUB;
+    int64_t row = (int64_t)blockIdx.x * rows_per_block + sub_id;
+    const int64_t stride = (int64_t)gridDim.x * rows_per_block;
+    const int64_t nvec = spec.row_bytes / (int64_t)sizeof(VecT);
+
+    // copy output row r = translated row idx, whose table entry is e
+    auto copy_row = [&](int64_t r, int64_t idx, uint64_t e) {
+        if (idx < 0) return;
+        // shard search as a uniform loop with selects: spec.ends[i] and
+        // spec.ptrs[i] stay scalar loads of the kernel arguments.  Indexing
+        // them by a per-lane shard number is a vector load, one more
+        // dependent load in front of every row; with it this kernel gained
+        // nothing over copy_rows_kernel (profiles/GATHER_ROW_REUSE.md).
+        const char* base = nullptr;  // stays null: out of range, or a
+        int64_t start = 0;           //   shard of the HBM-tier launch
+        for (int i = 0; i < spec.nshards; ++i) {
+            const int64_t lo = (i == 0) ? 0 : spec.ends[i - 1];
+            if (idx >= lo && idx < spec.ends[i] &&
+                ((spec.access_mask >> i) & 1u)) {
+                base = spec.ptrs[i];
+                start = lo;
+            }
+        }
+        if (!base) return;
+        const char* src_row = base + (idx - start) * spec.row_bytes;
+
+        const int64_t t = idx - ru.row_base;
+        const bool tracked = t >= 0 && t < ru.rows;
+        if (tracked) {
+            const uint32_t e_seq = (uint32_t)(e >> 32);
+            const int64_t e_row = (int64_t)(e & 0xffffffffu);
+            // Only an entry 1..kReuseWindow gathers old names a source.
+            // Duplicate ids inside one batch: another sub-group may have
+            // stored this gather's own sequence already (age 0); such an
+            // entry is never a source, the row then comes from the host.
+            const uint32_t age = ru.seq - e_seq;
+            if (e_seq != 0 && age >= 1 && age <= (uint32_t)kReuseWindow) {
+                const char* p = age == 1 ? ru.src[0] : ru.src[1];
+                const int64_t p_rows =
+                    age == 1 ? ru.src_rows[0] : ru.src_rows[1];
+                if (p && e_row < p_rows) src_row = p + e_row * spec.row_bytes;
+            }
+        }
+        const VecT* src = (const VecT*)src_row;
+        VecT* dst = (VecT*)(out + r * spec.row_bytes);
+        for (int64_t j = lane; j < nvec; j += SUB) dst[j] = src[j];
+        // Duplicate ids: two sub-groups may store to one entry; both
+        // values name a valid row of this gather's output.
+        if (tracked && lane == 0)
+            ru.table[t] = ((uint64_t)ru.seq << 32) | (uint64_t)r;
+    };
+
+    for (; row < n; row += stride) {
+        int64_t idx = indices[row];
+        if (order) {
+            if (idx < 0 || idx >= order_n) continue;
+            idx = order[idx];
+        }
+        const int64_t t = idx - ru.row_base;
+        // untracked rows (hot, out of range, negative): no table access
+        copy_row(row, idx, (t >= 0 && t < ru.rows) ? ru.table[t] : 0);
+    }
+}
+
 inline int grid_for(int64_t work, int per_block, int max_blocks) {
     int64_t blocks = (work + per_block - 1) / per_block;
     if (blocks > max_blocks) blocks = max_blocks;
@@ -107,7 +186,7 @@ template <typename VecT, bool SCATTER>
 void dispatch_sub(hipStream_t s, const GatherSpec& spec,
                   const int64_t* indices, int64_t n, char* other,
                   const int64_t* n_dev, const int64_t* order,
-                  int64_t order_n) {
+                  int64_t order_n, const GatherReuse* ru = nullptr) {
     int64_t nvec = spec.row_bytes / (int64_t)sizeof(VecT);
     int sub = 4;
     while (sub < 64 && sub < nvec) sub *= 2;  // cover the row in ~1 pass
@@ -117,6 +196,13 @@ void dispatch_sub(hipStream_t s, const GatherSpec& spec,
     switch (sub) {
 #define QK_CASE(S)                                                          \
     case S:                                                                 \
+        if constexpr (!SCATTER) {                                           \
+            if (ru) {                                                       \
+                copy_rows_reuse_kernel<VecT, S><<<grid, BLOCK, 0, s>>>(     \
+                    spec, *ru, indices, n, other, n_dev, order, order_n);   \
+                break;                                                      \
+            }                                                               \
+        }                                                                   \
         copy_rows_kernel<VecT, S, SCATTER><<<grid, BLOCK, 0, s>>>(          \
             spec, indices, n, other, n_dev, order, order_n);                \
         break;
@@ -129,20 +215,21 @@ void dispatch_sub(hipStream_t s, const GatherSpec& spec,
 template <bool SCATTER>
 void copy_rows(hipStream_t s, const GatherSpec& spec, const int64_t* indices,
                int64_t n, char* other, const int64_t* n_dev,
-               const int64_t* order, int64_t order_n) {
+               const int64_t* order, int64_t order_n,
+               const GatherReuse* ru = nullptr) {
     if (n == 0 || spec.nshards == 0) return;
     if (spec.row_bytes % 16 == 0)
         dispatch_sub<vec16, SCATTER>(s, spec, indices, n, other, n_dev,
-                                     order, order_n);
+                                     order, order_n, ru);
     else if (spec.row_bytes % 8 == 0)
         dispatch_sub<uint64_t, SCATTER>(s, spec, indices, n, other, n_dev,
-                                        order, order_n);
+                                        order, order_n, ru);
     else if (spec.row_bytes % 4 == 0)
         dispatch_sub<uint32_t, SCATTER>(s, spec, indices, n, other, n_dev,
-                                        order, order_n);
+                                        order, order_n, ru);
     else
         dispatch_sub<uint8_t, SCATTER>(s, spec, indices, n, other, n_dev,
-                                       order, order_n);
+                                       order, order_n, ru);
 }
 
 }  // namespace
@@ -152,6 +239,19 @@ void launch_gather(hipStream_t s, const GatherSpec& spec,
                    const int64_t* n_dev, const int64_t* order,
                    int64_t order_n) {
     copy_rows<false>(s, spec, indices, n, out, n_dev, order, order_n);
+}
+
+void launch_gather_reuse(hipStream_t s, const GatherSpec& spec,
+                         const int64_t* indices, int64_t n, char* out,
+                         const int64_t* n_dev, const int64_t* order,
+                         int64_t order_n, const GatherReuse& ru) {
+    // the kernel reads *n_dev unconditionally and packs the output row
+    // into the low 32 bits of a table entry
+    if (!n_dev || !ru.table || ru.seq == 0 || n > (int64_t)UINT32_MAX)
+        throw std::runtime_error(
+            "launch_gather_reuse: needs a device-side count, a table, a "
+            "sequence number >= 1 and at most 2^32-1 rows");
+    copy_rows<false>(s, spec, indices, n, out, n_dev, order, order_n, &ru);
 }
 
 void launch_scatter(hipStream_t s, const GatherSpec& spec,

@@ -17,7 +17,9 @@
 #include <algorithm>
 #include <atomic>
 #include <condition_variable>
+#include <climits>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <random>
@@ -702,6 +704,30 @@ class ShardTensorItem {
     }
 };
 
+// Row reuse state of one ShardTensor (qk::GatherReuse has the table
+// layout).  Created lazily by the first reusing gather, guarded by
+// ShardTensor::reuse_mu_.  Reusing gathers are numbered from 1; gather s
+// enters ring[s % kReuseWindow], so the ring always holds the last
+// kReuseWindow of them.
+struct ReuseSlot {
+    torch::Tensor out;          // Lifetime: this reference keeps a source's
+                                // storage from being recycled
+    uint32_t seq = 0;           // 0: never used
+    hipEvent_t done = nullptr;  // recorded after the gather's kernels
+};
+
+struct ReuseState {
+    torch::Tensor table;        // int64 [rows], zero-initialised
+    int64_t row_base = 0, rows = 0;
+    uint32_t next_seq = 1;
+    uint32_t floor = 0;         // gathers <= floor are no sources any more
+    ReuseSlot ring[qk::kReuseWindow];
+    ~ReuseState() {
+        for (auto& slot : ring)
+            if (slot.done) (void)hipEventDestroy(slot.done);
+    }
+};
+
 class ShardTensor {
   public:
     explicit ShardTensor(int current_device) : device_(current_device) {}
@@ -723,6 +749,10 @@ class ShardTensor {
         tensor = tensor.contiguous();
         TORCH_CHECK(tensor.dim() >= 1, "need at least 1-d tensor");
         init_row_meta(tensor);
+        // Writes to the store: no earlier gather output is a reuse source
+        // (a new host shard also moves the table's row range, which the
+        // next reusing gather notices)
+        drop_reuse_sources();
         ShardItem item;
         item.rows = tensor.size(0);
         item.device = target_device;
@@ -823,14 +853,29 @@ class ShardTensor {
 
     // n_dev: 1-element int64 CUDA tensor holding the exact row count
     // (indices is upper-bound sized); enables fully async chains.
+    // reuse: pinned-host rows that one of the last two reusing gathers of
+    // this store also fetched are copied from that gather's output in HBM
+    // (see ReuseState).  The caller must leave a returned tensor
+    // unmodified until two further reusing gathers have been issued.
     torch::Tensor gather_n(torch::Tensor indices, torch::Tensor n_dev,
-                           c10::optional<torch::Tensor> order) {
+                           c10::optional<torch::Tensor> order, bool reuse) {
         return gather_impl(device_, indices, n_dev,
-                           order.value_or(torch::Tensor()));
+                           order.value_or(torch::Tensor()), reuse);
+    }
+
+    // No earlier gather output is a reuse source from here on.
+    void drop_reuse_sources() {
+        std::lock_guard<std::mutex> lk(reuse_mu_);
+        if (!reuse_) return;
+        reuse_->floor = reuse_->next_seq - 1;
+        // safe to let go: every gather that read a source recorded its
+        // stream on the source's storage when it was launched
+        for (auto& slot : reuse_->ring) slot.out = torch::Tensor();
     }
 
     torch::Tensor gather_impl(int dev, torch::Tensor indices,
-                              torch::Tensor n_dev_t, torch::Tensor order_t) {
+                              torch::Tensor n_dev_t, torch::Tensor order_t,
+                              bool reuse_wanted = false) {
         DeviceScope g(dev);
         indices = indices.contiguous();
         TORCH_CHECK(indices.device().is_cuda(), "indices must be on GPU");
@@ -922,14 +967,39 @@ class ShardTensor {
             }
             QK_CHECK_HIP(hipEventRecord(ev.first, cur.stream()));
             QK_CHECK_HIP(hipStreamWaitEvent(side.stream(), ev.first, 0));
-            qk::launch_gather(cur.stream(), hs, indices.data_ptr<int64_t>(),
-                              n, (char*)out.data_ptr(), n_dev, order,
-                              order_n);
+            // Row reuse scope: only the executing device's own store with
+            // a device-side count (the zero-sync chain).  Capture: a
+            // gather issued while the stream is capturing neither reads
+            // nor writes the table and does not enter the ring; a replay
+            // would otherwise freeze a sequence number into the graph.
+            const bool reuse = reuse_wanted && reuse_enabled() &&
+                               dev == device_ && n_dev != nullptr &&
+                               n > 0 && cs == hipStreamCaptureStatusNone;
+            // held until this gather's slot carries its event, so another
+            // thread's reusing gather never sees a half-entered slot
+            std::unique_lock<std::mutex> reuse_lk;
+            ReuseSlot* slot = nullptr;
+            if (reuse) {
+                reuse_lk = std::unique_lock<std::mutex>(reuse_mu_);
+                slot = launch_host_reuse(cur, hs, host_mask, indices, n, out,
+                                         n_dev, order, order_n);
+            } else {
+                qk::launch_gather(cur.stream(), hs,
+                                  indices.data_ptr<int64_t>(), n,
+                                  (char*)out.data_ptr(), n_dev, order,
+                                  order_n);
+            }
             qk::launch_gather(side.stream(), ds, indices.data_ptr<int64_t>(),
                               n, (char*)out.data_ptr(), n_dev, order,
                               order_n);
             QK_CHECK_HIP(hipEventRecord(ev.second, side.stream()));
             QK_CHECK_HIP(hipStreamWaitEvent(cur.stream(), ev.second, 0));
+            if (slot) {
+                // after the join: the event covers both tiers' kernels
+                QK_CHECK_HIP(hipEventRecord(slot->done, cur.stream()));
+                slot->out = out;
+                reuse_lk.unlock();
+            }
             // caching-allocator hazard: out/indices are used on `side`.
             // (Tensor::record_stream wants a masquerading-as-CUDA stream;
             // go to the HIP allocator directly.)  Under hipGraph capture
@@ -952,8 +1022,105 @@ class ShardTensor {
         return out;
     }
 
+    // QUIVER_GATHER_REUSE=0 forces row reuse off (A/B runs of one build)
+    static bool reuse_enabled() {
+        static bool on = [] {
+            const char* e = getenv("QUIVER_GATHER_REUSE");
+            return !(e && atoi(e) == 0);
+        }();
+        return on;
+    }
+
+    // Host-tier launch of a reusing gather on `cur`; reuse_mu_ is held by
+    // the caller.  Returns the ring slot this gather enters; the caller
+    // records slot->done after the tiers have joined and stores `out`.
+    ReuseSlot* launch_host_reuse(c10::hip::HIPStream cur,
+                                 const qk::GatherSpec& hs, uint32_t host_mask,
+                                 const torch::Tensor& indices, int64_t n,
+                                 const torch::Tensor& out,
+                                 const int64_t* n_dev, const int64_t* order,
+                                 int64_t order_n) {
+        constexpr int W = qk::kReuseWindow;
+        // a table entry keeps the output row in 32 bits
+        TORCH_CHECK(n <= (int64_t)UINT32_MAX,
+                    "gather_n(reuse=True): more than 2^32-1 rows");
+        int64_t lo = INT64_MAX, hi = 0;
+        for (int s = 0; s < hs.nshards; ++s) {
+            if (!((host_mask >> s) & 1u)) continue;
+            lo = std::min(lo, s == 0 ? (int64_t)0 : hs.ends[s - 1]);
+            hi = std::max(hi, hs.ends[s]);
+        }
+        if (!reuse_ || reuse_->row_base != lo || reuse_->rows != hi - lo) {
+            // first reusing gather, or the host tier's rows have moved
+            // (append).  A replaced table is still safe under kernels in
+            // flight: every launch records its stream on the table.
+            auto st = std::make_unique<ReuseState>();
+            st->table = torch::zeros(
+                {hi - lo}, torch::TensorOptions().dtype(torch::kInt64).device(
+                               out.device()));
+            st->row_base = lo;
+            st->rows = hi - lo;
+            reuse_ = std::move(st);
+        }
+        ReuseState& st = *reuse_;
+        // Ordering: the sources were written, and the table last used, by
+        // the previous reusing gathers, which may have run on other
+        // streams (batch B-1 runs on the other prefetch stream).  Waiting
+        // on every slot's event, source or not, also keeps the table with
+        // one kernel at a time.
+        for (auto& slot : st.ring)
+            if (slot.seq != 0 && slot.done)
+                QK_CHECK_HIP(hipStreamWaitEvent(cur.stream(), slot.done, 0));
+        if (st.next_seq == UINT32_MAX) {
+            // sequence numbers exhausted: start over with an empty table
+            QK_CHECK_HIP(hipMemsetAsync(st.table.data_ptr(), 0,
+                                        (size_t)st.rows * 8, cur.stream()));
+            for (auto& slot : st.ring) {
+                slot.out = torch::Tensor();
+                slot.seq = 0;
+            }
+            st.next_seq = 1;
+            st.floor = 0;
+        }
+        const uint32_t seq = st.next_seq++;
+
+        qk::GatherReuse ru{};
+        ru.table = (uint64_t*)st.table.data_ptr<int64_t>();
+        ru.row_base = st.row_base;
+        ru.rows = st.rows;
+        ru.seq = seq;
+        for (int k = 0; k < W; ++k) {
+            const int64_t want = (int64_t)seq - 1 - k;
+            if (want < 1 || want <= (int64_t)st.floor) continue;
+            ReuseSlot& src = st.ring[want % W];
+            if (src.seq != (uint32_t)want || !src.out.defined()) continue;
+            ru.src[k] = (const char*)src.out.data_ptr();
+            ru.src_rows[k] = src.out.size(0);
+            // Lifetime: this stream reads the source.  Recorded now, long
+            // before the ring lets go of it, so once every reference is
+            // gone (a `del` in Python included) the allocator still holds
+            // the block back until this kernel has run.
+            c10::hip::HIPCachingAllocator::recordStream(
+                src.out.storage().data_ptr(), cur);
+        }
+        c10::hip::HIPCachingAllocator::recordStream(
+            st.table.storage().data_ptr(), cur);
+        qk::launch_gather_reuse(cur.stream(), hs, indices.data_ptr<int64_t>(),
+                                n, (char*)out.data_ptr(), n_dev, order,
+                                order_n, ru);
+        ReuseSlot& slot = st.ring[seq % W];
+        if (!slot.done)
+            QK_CHECK_HIP(hipEventCreateWithFlags(&slot.done,
+                                                 hipEventDisableTiming));
+        slot.seq = seq;
+        slot.out = torch::Tensor();  // set by the caller after the join
+        return &slot;
+    }
+
     void scatter_update(torch::Tensor indices, torch::Tensor src) {
         DeviceScope g(device_);
+        // Writes to the store: earlier gather outputs may hold old values
+        drop_reuse_sources();
         indices = indices.contiguous();
         src = src.contiguous();
         auto spec = build_spec(device_);
@@ -1181,6 +1348,9 @@ class ShardTensor {
     mutable std::unordered_map<int, std::pair<hipEvent_t, hipEvent_t>>
         split_events_;
     mutable std::unordered_map<int, c10::hip::HIPStream> side_streams_;
+    // row reuse of the host-tier gather (gather_n(reuse=True))
+    std::mutex reuse_mu_;
+    std::unique_ptr<ReuseState> reuse_;
     // pinned buffers for the CPU-staged host-tier gather
     torch::Tensor idx_pin_, pos_pin_, stage_pin_;
 };
@@ -1712,7 +1882,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              py::call_guard<py::gil_scoped_release>())
         .def("gather_n", &ShardTensor::gather_n, py::arg("indices"),
              py::arg("n_dev"), py::arg("order") = py::none(),
+             py::arg("reuse") = false,
              py::call_guard<py::gil_scoped_release>())
+        .def("drop_reuse_sources", &ShardTensor::drop_reuse_sources,
+             "no earlier gather output is a row-reuse source from here on")
         .def("access_mask_on", &ShardTensor::access_mask_on)
         .def("shard_ends", &ShardTensor::shard_ends)
         .def("scatter_update", &ShardTensor::scatter_update,

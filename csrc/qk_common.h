@@ -150,6 +150,33 @@ void launch_gather(hipStream_t s, const GatherSpec& spec,
                    const int64_t* n_dev = nullptr,
                    const int64_t* order = nullptr, int64_t order_n = 0);
 
+// Row reuse for the pinned-host tier: consecutive mini-batches share cold
+// rows, and the outputs of the last kReuseWindow gathers are still in HBM
+// when the next one runs, so a repeated row is copied from there instead
+// of crossing the PCIe link again.  `table` has one entry per row of
+// [row_base, row_base + rows) (the host-tier rows, after `order`):
+// (gather sequence number << 32) | row in that gather's output, sequence
+// 0 meaning "never gathered".
+constexpr int kReuseWindow = 2;
+struct GatherReuse {
+    uint64_t* table;
+    int64_t row_base, rows;
+    uint32_t seq;                      // this gather's sequence number, >= 1
+    const char* src[kReuseWindow];     // output of gather seq-1-k; null when
+    int64_t src_rows[kReuseWindow];    //   it may not be read; its row count
+};
+
+// launch_gather for a spec whose accessible shards are all pinned-host,
+// with row reuse: a row whose entry names one of ru.src is copied from
+// there, any other row from its shard; either way its entry is set to
+// (ru.seq, i).  n_dev is required, n must fit 32 bits.  The caller orders
+// this launch after the kernels that wrote ru.src and that last used
+// ru.table.
+void launch_gather_reuse(hipStream_t s, const GatherSpec& spec,
+                         const int64_t* indices, int64_t n, char* out,
+                         const int64_t* n_dev, const int64_t* order,
+                         int64_t order_n, const GatherReuse& ru);
+
 // Scatter-style update used by the python layer for cache fill / tests:
 // shard-resident rows only.  dst row indices[i] <- src[i].
 void launch_scatter(hipStream_t s, const GatherSpec& spec,

@@ -326,7 +326,7 @@ class Feature(object):
             return self.device_tensor_list[self.rank]
         return self.clique_tensor_list[self.topo.get_clique_id(self.rank)]
 
-    def gather_raw(self, node_idx, n_dev):
+    def gather_raw(self, node_idx, n_dev, reuse=False):
         """Async gather over an upper-bound-sized frontier: the exact row
         count is read by the kernel from the 1-element device tensor
         `n_dev` — no host synchronization anywhere on the path.  Slack
@@ -338,13 +338,19 @@ class Feature(object):
         up as one dependent load (no translated int64 temporary the size
         of the upper-bound frontier per batch).  Cold (pinned-host) rows
         run on the current stream at a capped grid, hot rows at full
-        grid on one cached side stream."""
+        grid on one cached side stream.
+
+        reuse=True lets cold rows that one of the last two reusing
+        gathers also fetched come from that gather's output in HBM; the
+        caller then must not modify a returned tensor in place until two
+        further reusing gathers have been issued (see
+        `ShardTensor.gather_n`)."""
         self.lazy_init_from_ipc_handle()
         if self.mmap_handle_ is not None:
             raise RuntimeError("gather_raw does not support the disk tier")
         node_idx = node_idx.to(self.rank)
         return self._shard_tensor().gather_n(node_idx, n_dev,
-                                             self.feature_order)
+                                             self.feature_order, reuse)
 
     def __getitem__(self, node_idx: torch.Tensor):
         self.lazy_init_from_ipc_handle()

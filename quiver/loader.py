@@ -87,8 +87,36 @@ class _GraphedChain:
 
 
 class TrainingPrefetcher:
+    """Iterates (n_id, batch_size, adjs, x) with the sample+gather chain of
+    the next `depth` batches running ahead of the consumer.
+
+    reuse_rows (default on): on the zero-sync chain, cold (pinned-host)
+    rows that one of the previous two batches also gathered are copied
+    from that batch's `x` in HBM instead of crossing the PCIe link again
+    (`Feature.gather_raw(reuse=True)`).  Contract: a yielded `x` is read
+    by the gathers of the next two batches, so it must not be modified in
+    place until two further batches have been yielded.  Reading it,
+    passing it to the model and dropping it are all fine.  Pass
+    `reuse_rows=False` to get an `x` that is the consumer's alone.
+
+    Reuse only pays where batches repeat cold rows, so it is applied only
+    while the store's host tier has at most REUSE_MAX_HOST_ROWS_PER_SLOT
+    rows per frontier slot of a batch; past that the per-row table lookup
+    costs more than the few repeats save (profiles/GATHER_ROW_REUSE.md).
+    """
+
+    # Two batches of at most n frontier rows cover at most 2n / host_rows
+    # of the host tier, which bounds the repeat share of a uniform draw;
+    # below a share of 10 % the saving is inside the run-to-run spread, so
+    # the break-even is near host_rows = 20 n.  Measured on either side:
+    # host_rows / n = 1.8 repeats 27.7 % of the cold rows and the step
+    # gains 13 %; 87 repeats 2.5 % and the step loses 21 %.
+    REUSE_MAX_HOST_ROWS_PER_SLOT = 16
+
     def __init__(self, sampler, feature, seed_batches, depth=2, device=None,
-                 num_streams=1):
+                 num_streams=1, reuse_rows=True):
+        self.reuse_rows = bool(reuse_rows)
+        self._host_rows = None
         self.sampler = sampler
         self.feature = feature
         self.seed_batches = seed_batches
@@ -122,7 +150,39 @@ class TrainingPrefetcher:
                 pass  # lazy IPC store: decided on first produce instead
         return True
 
+    def _gather_raw(self, frontier, n_dev):
+        if not self.reuse_rows:
+            return self.feature.gather_raw(frontier, n_dev)
+        if self._host_rows is None:
+            self.feature.lazy_init_from_ipc_handle()
+            st = self.feature._shard_tensor().shard_tensor
+            self._host_rows = sum(
+                r for r, d in zip(st.shard_rows(), st.shard_devices())
+                if d < 0)
+        reuse = (self._host_rows
+                 <= self.REUSE_MAX_HOST_ROWS_PER_SLOT * frontier.numel())
+        return self.feature.gather_raw(frontier, n_dev, reuse=reuse)
+
+    def _drop_reuse_sources(self):
+        """An `x` yielded by an earlier iteration is not a reuse source
+        for this one (and the store stops holding the last two)."""
+        if not (self.reuse_rows and hasattr(self.feature, "_shard_tensor")):
+            return
+        try:
+            st = self.feature._shard_tensor()
+        except Exception:
+            return  # store not built yet: nothing to drop
+        if hasattr(st, "drop_reuse_sources"):
+            st.drop_reuse_sources()
+
     def __iter__(self):
+        self._drop_reuse_sources()
+        try:
+            yield from self._iterate()
+        finally:
+            self._drop_reuse_sources()
+
+    def _iterate(self):
         cur = torch.cuda.current_stream(self.device)
         # high-priority streams: the PCIe-latency-bound host gather needs
         # its blocks resident promptly even while model kernels churn CU
@@ -212,7 +272,7 @@ class TrainingPrefetcher:
                         if self.feature is not None:
                             raw, sizes_dev = tok[1], tok[2]
                             n_dev = sizes_dev[2 * len(raw) - 1:2 * len(raw)]
-                            x_ub = self.feature.gather_raw(raw[-1][0], n_dev)
+                            x_ub = self._gather_raw(raw[-1][0], n_dev)
                         ev = torch.cuda.Event()
                         ev.record(side)
                         pending.append(("tok", tok, x_ub, ev))

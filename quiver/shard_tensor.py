@@ -96,15 +96,29 @@ class ShardTensor:
         result = self.shard_tensor.gather_on(inter_device, request_nodes)
         wait_results.append((part_orders, result.to(self.current_device)))
 
-    def gather_n(self, nodes, n_dev, order=None):
+    def gather_n(self, nodes, n_dev, order=None, reuse=False):
         """Upper-bound gather with device-side exact count (async path);
         requires every shard to be directly accessible from this device.
-        order: optional int64 id -> row table applied inside the kernels."""
+        order: optional int64 id -> row table applied inside the kernels.
+
+        reuse: pinned-host rows that one of the last two reusing gathers
+        of this store also fetched are copied from that gather's output
+        in HBM instead of over the PCIe link.  The store keeps those two
+        outputs alive; the caller must not modify a returned tensor in
+        place until two further reusing gathers have been issued (or
+        `drop_reuse_sources()` was called).  `scatter_update` and
+        `append` retire every earlier output as a source.  Has no effect
+        on stores without both tiers, under stream capture, or with
+        QUIVER_GATHER_REUSE=0 in the environment."""
         if self._inaccessible_ranges():
             raise RuntimeError("gather_n: some shards need the cross-clique "
                                "pass; use __getitem__")
         nodes = nodes.to(self.current_device)
-        return self.shard_tensor.gather_n(nodes, n_dev, order)
+        return self.shard_tensor.gather_n(nodes, n_dev, order, reuse)
+
+    def drop_reuse_sources(self):
+        """No earlier `gather_n(reuse=True)` output is read again."""
+        self.shard_tensor.drop_reuse_sources()
 
     def __getitem__(self, nodes):
         return self.gather(nodes)
