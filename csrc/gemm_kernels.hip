@@ -191,117 +191,19 @@ tall_gemm_kernel(const float* __restrict__ A, const float* __restrict__ B,
     }
 }
 
-
-// 128x128 macro-tile variant for huge M: each wave owns a 64x64 quadrant
-// as 2x2 MFMA tiles (4 accumulators), 64 MFMAs per barrier — 4x the
-// compute per load round of the 64x64 kernel, which was convoy-bound at
-// these shallow K (PMC: 56% parked / 33% issue-stall).
-constexpr int BM2 = 128;
-constexpr int BN2 = 128;
-constexpr int BP2 = BN2 + 4;
-
-__global__ void __launch_bounds__(NT)
-tall_gemm128_kernel(const float* __restrict__ A, const float* __restrict__ B,
-                    const float* __restrict__ bias, float* __restrict__ C,
-                    int64_t M, int K, int N, int tn_) {
-    __shared__ float As[2][BM2][AP];
-    __shared__ float Bs[2][BK][BP2];
-
-    const int n_xcd = 8;
-    const int xcd = blockIdx.x % n_xcd;
-    const int slot = blockIdx.x / n_xcd;
-    const int nt = slot % tn_;
-    const int walker = slot / tn_;
-    const int walkers = (int)(gridDim.x / (n_xcd * tn_));
-    const int64_t m_stride = (int64_t)n_xcd * walkers * BM2;
-    const int n0 = nt * BN2;
-    const int tid = threadIdx.x;
-    const int wave = tid / 64;
-    const int lane = tid % 64;
-    const int wm = (wave % 2) * 64;
-    const int wn = (wave / 2) * 64;
-    const int fcol = lane % 32;
-    const int fk = lane / 32;
-
-    const int n_out0 = n0 + wn + fcol;
-    const int n_out1 = n_out0 + 32;
-    const float badd0 = (bias && n_out0 < N) ? bias[n_out0] : 0.f;
-    const float badd1 = (bias && n_out1 < N) ? bias[n_out1] : 0.f;
-
-    float4 ra[4], rb[4];
-    int64_t m0 = (int64_t)(xcd + n_xcd * walker) * BM2;
-    if (m0 >= M) return;
-    load_a<4>(A, M, K, m0, 0, tid, ra);
-    load_b<4, 32>(B, K, N, 0, n0, tid, rb);
-    store_a<4>(As[0], tid, ra);
-    store_b<4, 32, BP2>(Bs[0], tid, rb);
-    __syncthreads();
-
-    int buf = 0;
-    for (; m0 < M; m0 += m_stride) {
-        f32x16 acc00 = {}, acc01 = {}, acc10 = {}, acc11 = {};
-        for (int k0 = 0; k0 < K; k0 += BK) {
-            const bool more_k = k0 + BK < K;
-            const bool more_m = m0 + m_stride < M;
-            if (more_k) {
-                load_a<4>(A, M, K, m0, k0 + BK, tid, ra);
-                load_b<4, 32>(B, K, N, k0 + BK, n0, tid, rb);
-            } else if (more_m) {
-                load_a<4>(A, M, K, m0 + m_stride, 0, tid, ra);
-                load_b<4, 32>(B, K, N, 0, n0, tid, rb);
-            }
-#pragma unroll
-            for (int kk = 0; kk < BK; kk += 2) {
-                const float a0 = As[buf][wm + fcol][kk + fk];
-                const float a1 = As[buf][wm + 32 + fcol][kk + fk];
-                const float b0 = Bs[buf][kk + fk][wn + fcol];
-                const float b1 = Bs[buf][kk + fk][wn + 32 + fcol];
-                acc00 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc00,
-                                                             0, 0, 0);
-                acc01 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc01,
-                                                             0, 0, 0);
-                acc10 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc10,
-                                                             0, 0, 0);
-                acc11 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc11,
-                                                             0, 0, 0);
-            }
-            if (more_k || more_m) {
-                store_a<4>(As[buf ^ 1], tid, ra);
-                store_b<4, 32, BP2>(Bs[buf ^ 1], tid, rb);
-            }
-            __syncthreads();
-            buf ^= 1;
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int dm = (r & 3) + 8 * (r >> 2) + 4 * fk;
-            const int64_t mr0 = m0 + wm + dm;
-            const int64_t mr1 = mr0 + 32;
-            if (mr0 < M) {
-                if (n_out0 < N) C[mr0 * N + n_out0] = acc00[r] + badd0;
-                if (n_out1 < N) C[mr0 * N + n_out1] = acc01[r] + badd1;
-            }
-            if (mr1 < M) {
-                if (n_out0 < N) C[mr1 * N + n_out0] = acc10[r] + badd0;
-                if (n_out1 < N) C[mr1 * N + n_out1] = acc11[r] + badd1;
-            }
-        }
-    }
-}
-
 }  // namespace
 
 void launch_tall_gemm(hipStream_t s, const float* A, const float* B,
                       const float* bias, float* C, int64_t M, int K, int N) {
-    if (M == 0 || K == 0 || N == 0) return;
-    // 128x128 tiles measured SLOWER on the huge-frontier shapes (1461
-    // vs 1111 us at 1.06Mx100x256): LDS doubles -> 2 blocks/CU and the
-    // lost concurrency outweighs 4x compute per barrier.  Kernel kept
-    // for reference/perf archaeology; routing stays on 64x64.
-    const bool big = false;
-    const int bm = big ? BM2 : BM, bn = big ? BN2 : BN;
-    int64_t tm = (M + bm - 1) / bm;
-    int tn = (N + bn - 1) / bn;
+    // K == 0 still launches: every guarded load yields zeros and the
+    // kernel stores the bias (or zeros), so C is always defined.
+    if (M == 0 || N == 0) return;
+    // A 128x128-tile variant (4 accumulators per wave) measured SLOWER on
+    // the huge-frontier shapes (1461 vs 1111 us at 1.06Mx100x256): LDS
+    // doubles -> 2 blocks/CU and the lost concurrency outweighs 4x
+    // compute per barrier.  It was removed; routing stays on 64x64.
+    int64_t tm = (M + BM - 1) / BM;
+    int tn = (N + BN - 1) / BN;
     // walkers per (xcd, n-tile): enough blocks to fill the chip several
     // times over, few enough that each walks multiple m-tiles
     int64_t walkers = 4096 / (8 * tn);
@@ -309,10 +211,7 @@ void launch_tall_gemm(hipStream_t s, const float* A, const float* B,
     if (walkers > need) walkers = need;
     if (walkers < 1) walkers = 1;
     unsigned gx = (unsigned)(8 * tn * walkers);
-    if (big)
-        tall_gemm128_kernel<<<gx, NT, 0, s>>>(A, B, bias, C, M, K, N, tn);
-    else
-        tall_gemm_kernel<<<gx, NT, 0, s>>>(A, B, bias, C, M, K, N, tn);
+    tall_gemm_kernel<<<gx, NT, 0, s>>>(A, B, bias, C, M, K, N, tn);
     QK_CHECK_HIP(hipGetLastError());
 }
 

@@ -1491,6 +1491,23 @@ torch::Tensor segment_mean_prefix_backward(
                                       n_src);
 }
 
+// Front end of the two dense GEMM bindings, to the SegmentCall standard:
+// every operand is an fp32 CUDA tensor of the stated rank on the first
+// operand's device, checked before anything is allocated or launched.
+// Nothing here reads device memory.
+static torch::Tensor gemm_arg(const char* op, const char* name,
+                              const torch::Tensor& t, int64_t dim,
+                              const torch::Tensor* first) {
+    TORCH_CHECK(t.is_cuda() && t.dim() == dim &&
+                t.scalar_type() == torch::kFloat32 &&
+                (!first || t.device() == first->device()),
+                op, ": ", name, " must be a ", dim,
+                "-D CUDA tensor of float32",
+                first ? " on the first operand's device" : "", ", got ",
+                t.scalar_type(), " ", t.sizes(), " on ", t.device());
+    return t.contiguous();
+}
+
 // Tall-skinny weight gradient: (A^T @ B, optional column-sums of A).
 // A [K×M] (grad_out), B [K×N] (layer input), K = frontier size.
 // Deterministic: split-K partials land in a workspace (torch pool
@@ -1498,21 +1515,29 @@ torch::Tensor segment_mean_prefix_backward(
 std::tuple<torch::Tensor, torch::Tensor> wgrad(torch::Tensor a,
                                                torch::Tensor b,
                                                bool want_bias) {
-    TORCH_CHECK(a.is_cuda() && b.is_cuda() && a.dim() == 2 && b.dim() == 2 &&
-                a.size(0) == b.size(0) &&
-                a.dtype() == torch::kFloat32 &&
-                b.dtype() == torch::kFloat32,
-                "wgrad: fp32 CUDA 2-D tensors with matching K expected");
-    a = a.contiguous();
-    b = b.contiguous();
+    a = gemm_arg("wgrad", "a", a, 2, nullptr);
+    b = gemm_arg("wgrad", "b", b, 2, &a);
+    TORCH_CHECK(a.size(0) == b.size(0), "wgrad: a has ", a.size(0),
+                " rows, b has ", b.size(0));
+    TORCH_CHECK(a.size(1) <= INT_MAX && b.size(1) <= INT_MAX,
+                "wgrad: more than 2^31-1 columns");
+    DeviceScope scope(a.get_device());
+    hipStream_t stream =
+        c10::hip::getCurrentHIPStream(a.get_device()).stream();
     int64_t k = a.size(0);
     int m = (int)a.size(1), n = (int)b.size(1);
+    if (k == 0 || m == 0 || n == 0) {
+        // an empty sum is zero, and the plan would divide by zero here;
+        // with only N empty the column sums of A are still wanted
+        return {torch::zeros({m, n}, a.options()),
+                want_bias ? a.sum(0) : torch::Tensor()};
+    }
     auto c = torch::empty({m, n}, a.options());
     auto bias = want_bias ? torch::empty({m}, a.options()) : torch::Tensor();
     auto plan = qk::wgrad_plan(k, m, n);
     auto ws = torch::empty({plan.ws_floats}, a.options());
-    qk::launch_wgrad(current_stream(), a.data_ptr<float>(),
-                     b.data_ptr<float>(), c.data_ptr<float>(),
+    qk::launch_wgrad(stream, a.data_ptr<float>(), b.data_ptr<float>(),
+                     c.data_ptr<float>(),
                      want_bias ? bias.data_ptr<float>() : nullptr, k, m, n,
                      plan, ws.data_ptr<float>());
     return {c, bias};
@@ -1636,27 +1661,30 @@ std::tuple<torch::Tensor, torch::Tensor> gat_alpha_backward(
 // for the data-grad, so both read coalesced.
 torch::Tensor tall_gemm(torch::Tensor a, torch::Tensor b_kmajor,
                         c10::optional<torch::Tensor> bias_opt) {
-    torch::Tensor bias =
-        bias_opt.has_value() ? *bias_opt : torch::Tensor();
-    TORCH_CHECK(a.is_cuda() && a.dim() == 2 &&
-                a.dtype() == torch::kFloat32 &&
-                b_kmajor.dtype() == torch::kFloat32 &&
-                a.size(1) == b_kmajor.size(0),
-                "tall_gemm: fp32 [M,K] @ [K,N] expected");
-    a = a.contiguous();
-    b_kmajor = b_kmajor.contiguous();
+    a = gemm_arg("tall_gemm", "a", a, 2, nullptr);
+    b_kmajor = gemm_arg("tall_gemm", "b_kmajor", b_kmajor, 2, &a);
+    TORCH_CHECK(a.size(1) == b_kmajor.size(0), "tall_gemm: a has ",
+                a.size(1), " columns, b_kmajor has ", b_kmajor.size(0),
+                " rows");
+    TORCH_CHECK(a.size(1) <= INT_MAX && b_kmajor.size(1) <= INT_MAX,
+                "tall_gemm: K or N above 2^31-1");
     const int64_t m = a.size(0);
     const int k = (int)a.size(1), n = (int)b_kmajor.size(1);
-    auto c = torch::empty({m, (int64_t)n}, a.options());
+    torch::Tensor bias;
     const float* bp = nullptr;
-    if (bias.defined() && bias.numel() > 0) {
-        bias = bias.contiguous();
-        TORCH_CHECK(bias.numel() == n, "bias size mismatch");
+    if (bias_opt.has_value() && bias_opt->defined()) {
+        bias = gemm_arg("tall_gemm", "bias", *bias_opt, 1, &a);
+        TORCH_CHECK(bias.numel() == n, "tall_gemm: bias has ", bias.numel(),
+                    " elements for N = ", n);
         bp = bias.data_ptr<float>();
     }
-    qk::launch_tall_gemm(current_stream(), a.data_ptr<float>(),
-                         b_kmajor.data_ptr<float>(), bp,
-                         c.data_ptr<float>(), m, k, n);
+    DeviceScope scope(a.get_device());
+    auto c = torch::empty({m, (int64_t)n}, a.options());
+    // M == 0 or N == 0 launches nothing; K == 0 stores the bias (or zeros)
+    qk::launch_tall_gemm(
+        c10::hip::getCurrentHIPStream(a.get_device()).stream(),
+        a.data_ptr<float>(), b_kmajor.data_ptr<float>(), bp,
+        c.data_ptr<float>(), m, k, n);
     return c;
 }
 

@@ -246,6 +246,9 @@ wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ C,
 
 WgradPlan wgrad_plan(int64_t K, int M, int N) {
     WgradPlan p{};
+    // an empty problem has no tiles and no chunks (launch_wgrad returns
+    // at once); the divisions below need all three non-zero
+    if (K <= 0 || M <= 0 || N <= 0) return p;
     p.tm = (M + BM - 1) / BM;
     p.tn = (N + BN - 1) / BN;
     // size the K split so the grid comfortably covers 256 CUs x 8 XCDs

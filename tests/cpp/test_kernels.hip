@@ -500,14 +500,18 @@ void test_segment_mean() {
     printf("ok test_segment_mean\n");
 }
 
-void test_wgrad() {
+// integer_valued: operands are integers in [-8, 8], so every partial sum
+// (|sum| <= 64*K = 1.92e6 < 2^24) is exact in fp32 in any summation order
+// and the result must EQUAL the double loop.
+void test_wgrad(bool integer_valued) {
     std::mt19937 rng(7);
     const int64_t K = 30000;
     const int M = 100, N = 130;  // non-multiples of the 64x64 tile
     std::vector<float> a(K * M), b(K * N);
     std::uniform_real_distribution<float> ud(-1.f, 1.f);
-    for (auto& v : a) v = ud(rng);
-    for (auto& v : b) v = ud(rng);
+    std::uniform_int_distribution<int> id(-8, 8);
+    for (auto& v : a) v = integer_valued ? (float)id(rng) : ud(rng);
+    for (auto& v : b) v = integer_valued ? (float)id(rng) : ud(rng);
     auto* d_a = dalloc<float>(a.size());
     auto* d_b = dalloc<float>(b.size());
     auto* d_c = dalloc<float>((size_t)M * N);
@@ -521,22 +525,57 @@ void test_wgrad() {
     auto c = d2h(d_c, (size_t)M * N);
     auto bias = d2h(d_bias, M);
     // CPU reference in double
-    double tol = 1e-4 * std::sqrt((double)K) * 10;
+    const double tol = 1e-4 * std::sqrt((double)K) * 10;
+    auto close = [&](double got, double want) {
+        return integer_valued ? got == want : std::abs(got - want) < tol;
+    };
     for (int mm = 0; mm < M; ++mm) {
         double bs = 0;
         for (int64_t k = 0; k < K; ++k) bs += a[k * M + mm];
-        REQUIRE(std::abs(bias[mm] - bs) < tol);
+        REQUIRE(close(bias[mm], bs));
     }
-    for (int mm = 0; mm < M; mm += 7)
+    for (int mm = 0; mm < M; mm += integer_valued ? 1 : 7)
         for (int nn = 0; nn < N; ++nn) {
             double acc = 0;
             for (int64_t k = 0; k < K; ++k)
                 acc += (double)a[k * M + mm] * b[k * N + nn];
-            REQUIRE(std::abs(c[mm * N + nn] - acc) < tol);
+            REQUIRE(close(c[mm * N + nn], acc));
         }
     hipFree(d_a); hipFree(d_b); hipFree(d_c); hipFree(d_bias);
     hipFree(d_ws);
-    printf("ok test_wgrad\n");
+    printf("ok test_wgrad (%s)\n", integer_valued ? "integer" : "float");
+}
+
+// Integer-valued operands in [-8, 8]: |sum| <= 64*K + 8 = 3016 < 2^24, so
+// the fp32 result is exact in any order and must equal the double loop.
+void test_tall_gemm() {
+    std::mt19937 rng(8);
+    const int64_t M = 200;         // 4 m-tiles, the last one ragged
+    const int K = 47, N = 100;     // ragged second k-stage, scalar A path
+    std::vector<float> a(M * K), b((size_t)K * N), bias(N);
+    std::uniform_int_distribution<int> id(-8, 8);
+    for (auto& v : a) v = (float)id(rng);
+    for (auto& v : b) v = (float)id(rng);
+    for (auto& v : bias) v = (float)id(rng);
+    auto* d_a = dalloc<float>(a.size());
+    auto* d_b = dalloc<float>(b.size());
+    auto* d_bias = dalloc<float>(N);
+    auto* d_c = dalloc<float>((size_t)M * N);
+    h2d(d_a, a);
+    h2d(d_b, b);
+    h2d(d_bias, bias);
+    qk::launch_tall_gemm(nullptr, d_a, d_b, d_bias, d_c, M, K, N);
+    QK_CHECK_HIP(hipDeviceSynchronize());
+    auto c = d2h(d_c, (size_t)M * N);
+    for (int64_t mm = 0; mm < M; ++mm)
+        for (int nn = 0; nn < N; ++nn) {
+            double acc = bias[nn];
+            for (int k = 0; k < K; ++k)
+                acc += (double)a[mm * K + k] * b[(size_t)k * N + nn];
+            REQUIRE((double)c[mm * N + nn] == acc);
+        }
+    hipFree(d_a); hipFree(d_b); hipFree(d_bias); hipFree(d_c);
+    printf("ok test_tall_gemm\n");
 }
 
 }  // namespace
@@ -554,7 +593,9 @@ int main() {
     test_cal_next();
     test_gather_scatter();
     test_segment_mean();
-    test_wgrad();
+    test_wgrad(false);
+    test_wgrad(true);
+    test_tall_gemm();
     printf("ALL C++ KERNEL TESTS PASSED\n");
     return 0;
 }
