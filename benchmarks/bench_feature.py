@@ -35,15 +35,34 @@ def skewed_batches(nodes, batch, iters, seed=3, alpha=2.0):
     return [torch.from_numpy(row) for row in ids]
 
 
+DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16,
+          "fp16": torch.float16}
+
+
 def bench(shape, cache, policy, device_list, batch=80_000, iters=50,
-          warmup=5, rank=0, sorted_ids=False):
+          warmup=5, rank=0, sorted_ids=False, dtype="fp32", quantize=None,
+          out_dtype=None):
+    """dtype: element type of the input rows (and of the store, unless
+    quantize="int8" packs them to a byte per channel plus 8 bytes per
+    row); out_dtype: what an int8 store's lookups return."""
     cfg = SHAPES[shape]
     g = torch.Generator().manual_seed(0)
-    feat = torch.randn(cfg["nodes"], cfg["dim"], generator=g)
+    feat = torch.randn(cfg["nodes"], cfg["dim"], generator=g).to(
+        DTYPES[dtype])
     feature = quiver.Feature(rank, device_list=device_list,
                              device_cache_size=cache, cache_policy=policy)
-    feature.from_cpu_tensor(feat)
-    row_bytes = cfg["dim"] * 4
+    if quantize is None:
+        feature.from_cpu_tensor(feat)
+        row_bytes = cfg["dim"] * feat.element_size()
+    else:
+        feature.from_cpu_tensor(
+            feat, quantize=quantize,
+            out_dtype=DTYPES[out_dtype] if out_dtype else None)
+        row_bytes = quiver.quant.packed_row_bytes(cfg["dim"])
+    del feat
+    st = feature._shard_tensor().shard_tensor
+    hot_rows = sum(r for r, d in zip(st.shard_rows(), st.shard_devices())
+                   if d >= 0)
     batches = [b.cuda() for b in skewed_batches(cfg["nodes"], batch,
                                                 warmup + iters)]
     if sorted_ids:
@@ -58,9 +77,16 @@ def bench(shape, cache, policy, device_list, batch=80_000, iters=50,
         total += out.numel() * out.element_size()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    # delivered: bytes of the rows handed to the caller; stored: bytes of
+    # the same rows as the store holds (and moves) them
+    stored = batch * iters * row_bytes
     return dict(shape=shape, cache=cache, policy=policy,
-                gbps=total / dt / 1e9, batch=batch, iters=iters,
-                row_bytes=row_bytes, sorted_ids=sorted_ids)
+                gbps=total / dt / 1e9, delivered_gbps=total / dt / 1e9,
+                stored_gbps=stored / dt / 1e9, ms_per_batch=dt / iters * 1e3,
+                batch=batch, iters=iters, row_bytes=row_bytes,
+                out_row_bytes=total // (batch * iters), dtype=dtype,
+                quantize=quantize, out_dtype=str(out.dtype),
+                hot_rows=hot_rows, sorted_ids=sorted_ids)
 
 
 if __name__ == "__main__":
@@ -72,6 +98,13 @@ if __name__ == "__main__":
     p.add_argument("--batch", type=int, default=80_000)
     p.add_argument("--iters", type=int, default=50)
     p.add_argument("--sorted", action="store_true")
+    p.add_argument("--dtype", default="fp32", choices=sorted(DTYPES),
+                   help="element type of the feature rows")
+    p.add_argument("--quantize", default=None, choices=["int8"],
+                   help="store 8-bit rows, dequantized in the gather")
+    p.add_argument("--out-dtype", default=None, choices=sorted(DTYPES),
+                   help="with --quantize: dtype of the gathered rows "
+                        "(default: --dtype)")
     args = p.parse_args()
     cfg = SHAPES[args.shape]
     cache = args.cache
@@ -82,5 +115,6 @@ if __name__ == "__main__":
     if args.policy == "p2p_clique_replicate":
         quiver.init_p2p(devices)
     res = bench(args.shape, cache, args.policy, devices, batch=args.batch,
-                iters=args.iters, sorted_ids=args.sorted)
+                iters=args.iters, sorted_ids=args.sorted, dtype=args.dtype,
+                quantize=args.quantize, out_dtype=args.out_dtype)
     print(json.dumps(res), flush=True)

@@ -15,6 +15,9 @@
 //    written or re-read per batch.
 //    (Alternatives measured for the pinned-host tier:
 //    profiles/GATHER_COLD_ROWS.md.)
+//  - 8-bit rows with a per-row scale and offset are dequantized by the
+//    gather itself (gather_dequant_kernel), so a cold row crosses the
+//    PCIe link at a byte per channel.
 #include <cstdlib>
 
 #include "qk_common.h"
@@ -232,7 +235,180 @@ void copy_rows(hipStream_t s, const GatherSpec& spec, const int64_t* indices,
                                        order, order_n, ru);
 }
 
+// ---- 8-bit rows, dequantized in the gather (layout: qk_common.h) ----
+
+// Storage type of an output element and the one rounding from fp32 to it.
+template <DequantElem E> struct DequantOut;
+template <> struct DequantOut<DequantElem::f32> {
+    using S = float;
+    static __device__ __forceinline__ S cvt(float f) { return f; }
+};
+template <> struct DequantOut<DequantElem::bf16> {
+    using S = uint16_t;
+    static __device__ __forceinline__ S cvt(float f) {
+        // nearest-even on the 16 dropped bits; the value is finite
+        uint32_t u = __float_as_uint(f);
+        u += 0x7fffu + ((u >> 16) & 1u);
+        return (uint16_t)(u >> 16);
+    }
+};
+template <> struct DequantOut<DequantElem::f16> {
+    using S = uint16_t;
+    static __device__ __forceinline__ S cvt(float f) {
+        const _Float16 h = (_Float16)f;  // v_cvt_f16_f32: nearest-even
+        return __builtin_bit_cast(uint16_t, h);
+    }
+};
+
+// Row assignment, shard search, order fold, n_dev and skipped rows as in
+// copy_rows_kernel.  A lane owns 16-byte code chunk j of its row, that is
+// output channels 16j .. 16j+15; a sub-group of SUB lanes covers the
+// row's code chunks, looping when there are more than SUB of them.
+// VEC is the number of output elements per store: the launcher picks the
+// widest power of two (at most 16 bytes) that divides dim, so every
+// output row and every chunk in it starts on a VEC-element boundary and
+// the live part of the last chunk is a whole number of stores.
+template <DequantElem E, int SUB, int VEC>
+__global__ void __launch_bounds__(BLOCK)
+gather_dequant_kernel(GatherSpec spec, const int64_t* __restrict__ indices,
+                      int64_t n, char* __restrict__ out, int dim,
+                      const int64_t* __restrict__ n_dev,
+                      const int64_t* __restrict__ order, int64_t order_n) {
+    using S = typename DequantOut<E>::S;
+    typedef S SV __attribute__((ext_vector_type(VEC)));
+    if (n_dev) n = min(n, *n_dev);
+    const int sub_id = threadIdx.x / SUB;
+    const int lane = threadIdx.x % SUB;
+    const int rows_per_block = BLOCK / SUB;
+    int64_t row = (int64_t)blockIdx.x * rows_per_block + sub_id;
+    const int64_t stride = (int64_t)gridDim.x * rows_per_block;
+    const int nchunk = (dim + 15) / 16;  // code chunks; the tail is apart
+
+    for (; row < n; row += stride) {
+        int64_t idx = indices[row];
+        if (order) {  // feature_order fold: one dependent load
+            if (idx < 0 || idx >= order_n) continue;
+            idx = order[idx];
+        }
+        if (idx < 0) continue;
+        int s = 0;
+        while (s < spec.nshards && idx >= spec.ends[s]) ++s;
+        if (s >= spec.nshards) continue;                  // out of range
+        if (!((spec.access_mask >> s) & 1u)) continue;    // peer pass fills it
+        const int64_t start = (s == 0) ? 0 : spec.ends[s - 1];
+        const char* shard_row =
+            spec.ptrs[s] + (idx - start) * spec.row_bytes;
+        const float2* tail = (const float2*)(shard_row + spec.row_bytes - 8);
+        S* dst_row = (S*)out + row * (int64_t)dim;
+        int j = lane;
+        if (j >= nchunk) continue;
+        // The lane's first code chunk and the tail are loaded back to back,
+        // before either is used: a pinned-host row costs one PCIe round
+        // trip, not two dependent ones.  (Written as a loop that loads
+        // both at its top, the compiler hoists the tail load and waits
+        // for it before the first code load.)
+        vec16 c = ((const vec16*)shard_row)[j];
+        const float2 sl = *tail;  // scale, lo
+        for (;;) {
+            const uint32_t w[4] = {(uint32_t)c.a, (uint32_t)(c.a >> 32),
+                                   (uint32_t)c.b, (uint32_t)(c.b >> 32)};
+            S o[16];
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const float q = (float)((w[k >> 2] >> (8 * (k & 3))) & 0xffu);
+                o[k] = DequantOut<E>::cvt(fmaf(q, sl.x, sl.y));
+            }
+            // the last chunk has dim % 16 live codes; padding and tail
+            // bytes are never stored
+            const int live = min(16, dim - 16 * j);
+            S* d = dst_row + 16 * j;
+#pragma unroll
+            for (int k = 0; k < 16; k += VEC) {
+                if (k < live) {
+                    if constexpr (VEC == 1) {
+                        d[k] = o[k];
+                    } else {
+                        SV v;
+#pragma unroll
+                        for (int e = 0; e < VEC; ++e) v[e] = o[k + e];
+                        *(SV*)(d + k) = v;
+                    }
+                }
+            }
+            // rows of more than SUB chunks: the sub-group's next pass
+            j += SUB;
+            if (j >= nchunk) break;
+            c = ((const vec16*)shard_row)[j];
+        }
+    }
+}
+
+template <DequantElem E, int VEC>
+void dequant_dispatch_sub(hipStream_t s, const GatherSpec& spec,
+                          const int64_t* indices, int64_t n, char* out,
+                          int dim, const int64_t* n_dev,
+                          const int64_t* order, int64_t order_n) {
+    const int nchunk = (dim + 15) / 16;
+    int sub = 4;
+    while (sub < 64 && sub < nchunk) sub *= 2;
+    // grid cap of the packed row size (gather_max_blocks is not retuned
+    // for these rows: profiles/GATHER_INT8.md)
+    int grid = grid_for(n, BLOCK / sub,
+                        gather_max_blocks(spec, n_dev != nullptr));
+    switch (sub) {
+#define QK_CASE(S)                                                          \
+    case S:                                                                 \
+        gather_dequant_kernel<E, S, VEC><<<grid, BLOCK, 0, s>>>(            \
+            spec, indices, n, out, dim, n_dev, order, order_n);             \
+        break;
+        QK_CASE(4) QK_CASE(8) QK_CASE(16) QK_CASE(32) QK_CASE(64)
+#undef QK_CASE
+    }
+    QK_CHECK_HIP(hipGetLastError());
+}
+
+template <DequantElem E>
+void dequant_dispatch_vec(hipStream_t s, const GatherSpec& spec,
+                          const int64_t* indices, int64_t n, char* out,
+                          int dim, const int64_t* n_dev,
+                          const int64_t* order, int64_t order_n) {
+    constexpr int kMaxVec = 16 / (int)sizeof(typename DequantOut<E>::S);
+    int vec = kMaxVec;
+    while (dim % vec != 0) vec /= 2;
+#define QK_CASE(V)                                                          \
+    if constexpr (V <= kMaxVec)                                             \
+        if (vec == V)                                                       \
+            return dequant_dispatch_sub<E, V>(s, spec, indices, n, out,     \
+                                              dim, n_dev, order, order_n);
+    QK_CASE(8) QK_CASE(4) QK_CASE(2) QK_CASE(1)
+#undef QK_CASE
+}
+
 }  // namespace
+
+void launch_gather_dequant(hipStream_t s, const GatherSpec& spec,
+                           const int64_t* indices, int64_t n, void* out,
+                           DequantElem out_elem, int64_t dim,
+                           const int64_t* n_dev, const int64_t* order,
+                           int64_t order_n) {
+    if (dim < 1 || dim > (int64_t)1 << 30 ||
+        spec.row_bytes != (dim + 8 + 15) / 16 * 16)
+        throw std::runtime_error(
+            "launch_gather_dequant: row_bytes must be round_up(dim + 8, 16)"
+            " (dim " + std::to_string(dim) + ", row_bytes " +
+            std::to_string(spec.row_bytes) + ")");
+    if (n == 0 || spec.nshards == 0) return;
+    switch (out_elem) {
+#define QK_CASE(E)                                                          \
+    case DequantElem::E:                                                    \
+        return dequant_dispatch_vec<DequantElem::E>(                        \
+            s, spec, indices, n, (char*)out, (int)dim, n_dev, order,        \
+            order_n);
+        QK_CASE(f32) QK_CASE(bf16) QK_CASE(f16)
+#undef QK_CASE
+    }
+    throw std::runtime_error("launch_gather_dequant: bad out_elem");
+}
 
 void launch_gather(hipStream_t s, const GatherSpec& spec,
                    const int64_t* indices, int64_t n, char* out,

@@ -688,18 +688,33 @@ class ShardTensorItem {
     std::vector<int64_t> row_shape;
     torch::Dtype dtype = torch::kFloat32;
     std::string handle;  // hipIpcMemHandle_t bytes
+    // shard of a dequantizing store (ShardTensor::set_dequant): row_shape
+    // and dtype above describe the packed rows, these the gathered ones
+    int64_t dequant_dim = 0;  // 0: ordinary store
+    torch::Dtype dequant_out = torch::kFloat32;
 
+    // 5 fields; a dequantizing store appends (dim, out_dtype), so handles
+    // of ordinary stores stay as they were
     py::tuple share_ipc() {
+        if (dequant_dim > 0)
+            return py::make_tuple(device, py::bytes(handle), rows, row_shape,
+                                  (int)dtype, dequant_dim, (int)dequant_out);
         return py::make_tuple(device, py::bytes(handle), rows,
                               row_shape, (int)dtype);
     }
     static ShardTensorItem from_ipc(py::tuple t) {
+        TORCH_CHECK(t.size() == 5 || t.size() == 7,
+                    "ShardTensorItem.from_ipc: expected 5 or 7 fields");
         ShardTensorItem it;
         it.device = t[0].cast<int>();
         it.handle = t[1].cast<std::string>();
         it.rows = t[2].cast<int64_t>();
         it.row_shape = t[3].cast<std::vector<int64_t>>();
         it.dtype = (torch::Dtype)t[4].cast<int>();
+        if (t.size() == 7) {
+            it.dequant_dim = t[5].cast<int64_t>();
+            it.dequant_out = (torch::Dtype)t[6].cast<int>();
+        }
         return it;
     }
 };
@@ -745,7 +760,39 @@ class ShardTensor {
         }
     }
 
+    // Make this (still empty) store a dequantizing one: its shards hold
+    // packed 8-bit rows (layout: qk_common.h, launch_gather_dequant) and
+    // every gather returns [n, dim] rows of out_dtype.
+    void set_dequant(int64_t dim, torch::Dtype out_dtype) {
+        TORCH_CHECK(shards_.empty() && !row_shape_init_,
+                    "set_dequant: the store already has shards");
+        TORCH_CHECK(dim >= 1 && dim <= ((int64_t)1 << 30),
+                    "set_dequant: bad dim ", dim);
+        (void)dequant_elem(out_dtype);  // throws on anything else
+        dequant_dim_ = dim;
+        dequant_out_ = out_dtype;
+    }
+    static int64_t packed_row_bytes(int64_t dim) {
+        return (dim + 8 + 15) / 16 * 16;
+    }
+    static qk::DequantElem dequant_elem(torch::Dtype dt) {
+        if (dt == torch::kFloat32) return qk::DequantElem::f32;
+        if (dt == torch::kBFloat16) return qk::DequantElem::bf16;
+        if (dt == torch::kFloat16) return qk::DequantElem::f16;
+        TORCH_CHECK(false, "dequantizing store: out_dtype must be float32, "
+                           "bfloat16 or float16");
+    }
+    void check_packed_rows(const torch::Tensor& t, const char* what) const {
+        TORCH_CHECK(t.scalar_type() == torch::kUInt8 && t.dim() == 2 &&
+                        t.size(1) == packed_row_bytes(dequant_dim_) &&
+                        t.is_contiguous(),
+                    what, ": a dequantizing store of dim ", dequant_dim_,
+                    " takes contiguous uint8 rows of ",
+                    packed_row_bytes(dequant_dim_), " bytes");
+    }
+
     void append(torch::Tensor tensor, int target_device) {
+        if (dequant_dim_ > 0) check_packed_rows(tensor, "append");
         tensor = tensor.contiguous();
         TORCH_CHECK(tensor.dim() >= 1, "need at least 1-d tensor");
         init_row_meta(tensor);
@@ -791,6 +838,7 @@ class ShardTensor {
         TORCH_CHECK(idx >= 0 && idx < (int)other.shards_.size(),
                     "append_from: no such shard");
         const ShardItem& s = other.shards_[idx];
+        check_same_dequant(other.dequant_dim_, other.dequant_out_);
         init_row_meta_from(other.row_shape_, other.dtype_);
         ShardItem item;
         item.dptr = s.dptr;
@@ -802,6 +850,11 @@ class ShardTensor {
 
     void append_item(const ShardTensorItem& it) {
         // open a peer shard exported from another process
+        check_same_dequant(it.dequant_dim, it.dequant_out);
+        if (dequant_dim_ > 0)
+            TORCH_CHECK(it.dtype == torch::kUInt8 && it.row_shape.size() == 1 &&
+                            it.row_shape[0] == packed_row_bytes(dequant_dim_),
+                        "append_item: packed row width does not match dim");
         init_row_meta_from(it.row_shape, it.dtype);
         ShardItem item;
         item.rows = it.rows;
@@ -827,6 +880,8 @@ class ShardTensor {
             it.rows = s.rows;
             it.row_shape = row_shape_;
             it.dtype = dtype_;
+            it.dequant_dim = dequant_dim_;
+            it.dequant_out = dequant_out_;
             hipIpcMemHandle_t h;
             DeviceScope g(s.device);
             QK_CHECK_HIP(hipIpcGetMemHandle(&h, s.dptr));
@@ -857,6 +912,7 @@ class ShardTensor {
     // this store also fetched are copied from that gather's output in HBM
     // (see ReuseState).  The caller must leave a returned tensor
     // unmodified until two further reusing gathers have been issued.
+    // Accepted and without effect on a dequantizing store.
     torch::Tensor gather_n(torch::Tensor indices, torch::Tensor n_dev,
                            c10::optional<torch::Tensor> order, bool reuse) {
         return gather_impl(device_, indices, n_dev,
@@ -882,11 +938,18 @@ class ShardTensor {
         TORCH_CHECK(indices.scalar_type() == torch::kInt64,
                     "indices must be int64");
         int64_t n = indices.numel();
+        // a dequantizing store returns [n, dim] of its out_dtype, whatever
+        // path the rows take below
+        const bool dq = dequant_dim_ > 0;
         std::vector<int64_t> shape = {n};
-        shape.insert(shape.end(), row_shape_.begin(), row_shape_.end());
+        if (dq)
+            shape.push_back(dequant_dim_);
+        else
+            shape.insert(shape.end(), row_shape_.begin(), row_shape_.end());
         auto out = torch::empty(
-            shape, torch::TensorOptions().dtype(dtype_).device(
-                       torch::Device(torch::kCUDA, dev)));
+            shape, torch::TensorOptions()
+                       .dtype(dq ? dequant_out_ : dtype_)
+                       .device(torch::Device(torch::kCUDA, dev)));
         auto spec = build_spec(dev);
         auto cur = c10::hip::getCurrentHIPStream(dev);
         const int64_t* n_dev = n_dev_t.defined()
@@ -915,7 +978,9 @@ class ShardTensor {
         host_mask &= spec.access_mask;
         uint32_t dev_mask = spec.access_mask & ~host_mask;
 
-        if (host_mask != 0 && dev_mask != 0 && staged_wanted(n)) {
+        // (never taken by a dequantizing store: the staging copies rows
+        // as stored and has no dequantizing step)
+        if (host_mask != 0 && dev_mask != 0 && !dq && staged_wanted(n)) {
             // CPU-staged host tier: zero-copy kernel reads of scattered
             // 400 B rows top out near ~11 GB/s (64 B uncached PCIe reads,
             // latency-bound).  Instead: HBM/xGMI rows via the full-grid
@@ -972,7 +1037,9 @@ class ShardTensor {
             // gather issued while the stream is capturing neither reads
             // nor writes the table and does not enter the ring; a replay
             // would otherwise freeze a sequence number into the graph.
-            const bool reuse = reuse_wanted && reuse_enabled() &&
+            // A dequantizing store accepts the flag and ignores it: the
+            // reuse kernel copies rows as stored.
+            const bool reuse = reuse_wanted && reuse_enabled() && !dq &&
                                dev == device_ && n_dev != nullptr &&
                                n > 0 && cs == hipStreamCaptureStatusNone;
             // held until this gather's slot carries its event, so another
@@ -984,14 +1051,11 @@ class ShardTensor {
                 slot = launch_host_reuse(cur, hs, host_mask, indices, n, out,
                                          n_dev, order, order_n);
             } else {
-                qk::launch_gather(cur.stream(), hs,
-                                  indices.data_ptr<int64_t>(), n,
-                                  (char*)out.data_ptr(), n_dev, order,
-                                  order_n);
+                launch_rows(cur.stream(), hs, indices.data_ptr<int64_t>(), n,
+                            out, n_dev, order, order_n);
             }
-            qk::launch_gather(side.stream(), ds, indices.data_ptr<int64_t>(),
-                              n, (char*)out.data_ptr(), n_dev, order,
-                              order_n);
+            launch_rows(side.stream(), ds, indices.data_ptr<int64_t>(), n,
+                        out, n_dev, order, order_n);
             QK_CHECK_HIP(hipEventRecord(ev.second, side.stream()));
             QK_CHECK_HIP(hipStreamWaitEvent(cur.stream(), ev.second, 0));
             if (slot) {
@@ -1015,11 +1079,26 @@ class ShardTensor {
                         order_t.storage().data_ptr(), side);
             }
         } else {
-            qk::launch_gather(cur.stream(), spec,
-                              indices.data_ptr<int64_t>(), n,
-                              (char*)out.data_ptr(), n_dev, order, order_n);
+            launch_rows(cur.stream(), spec, indices.data_ptr<int64_t>(), n,
+                        out, n_dev, order, order_n);
         }
         return out;
+    }
+
+    // One tier's gather launch: rows as stored, or dequantized for a
+    // store made by set_dequant.
+    void launch_rows(hipStream_t stream, const qk::GatherSpec& spec,
+                     const int64_t* indices, int64_t n, torch::Tensor& out,
+                     const int64_t* n_dev, const int64_t* order,
+                     int64_t order_n) const {
+        if (dequant_dim_ > 0)
+            qk::launch_gather_dequant(stream, spec, indices, n,
+                                      out.data_ptr(),
+                                      dequant_elem(dequant_out_),
+                                      dequant_dim_, n_dev, order, order_n);
+        else
+            qk::launch_gather(stream, spec, indices, n,
+                              (char*)out.data_ptr(), n_dev, order, order_n);
     }
 
     // QUIVER_GATHER_REUSE=0 forces row reuse off (A/B runs of one build)
@@ -1121,6 +1200,9 @@ class ShardTensor {
         DeviceScope g(device_);
         // Writes to the store: earlier gather outputs may hold old values
         drop_reuse_sources();
+        // A dequantizing store is written in its stored format only:
+        // packed rows (quantizing on the GPU is not provided).
+        if (dequant_dim_ > 0) check_packed_rows(src, "scatter_update");
         indices = indices.contiguous();
         src = src.contiguous();
         auto spec = build_spec(device_);
@@ -1263,7 +1345,10 @@ class ShardTensor {
 
     std::vector<int64_t> shape() const {
         std::vector<int64_t> s = {total_rows()};
-        s.insert(s.end(), row_shape_.begin(), row_shape_.end());
+        if (dequant_dim_ > 0)  // the gathered rows, not the packed ones
+            s.push_back(dequant_dim_);
+        else
+            s.insert(s.end(), row_shape_.begin(), row_shape_.end());
         return s;
     }
     int64_t total_rows() const {
@@ -1289,6 +1374,12 @@ class ShardTensor {
     void init_row_meta(const torch::Tensor& t) {
         std::vector<int64_t> rs(t.sizes().begin() + 1, t.sizes().end());
         init_row_meta_from(rs, t.scalar_type());
+    }
+    void check_same_dequant(int64_t dim, torch::Dtype out) const {
+        TORCH_CHECK(dim == dequant_dim_ &&
+                        (dim == 0 || out == dequant_out_),
+                    "shard and store disagree on dequantization (call "
+                    "set_dequant on the empty store first)");
     }
     void init_row_meta_from(const std::vector<int64_t>& rs, torch::Dtype dt) {
         if (row_shape_init_) {
@@ -1343,6 +1434,10 @@ class ShardTensor {
     torch::Dtype dtype_ = torch::kFloat32;
     int64_t row_bytes_ = 0;
     bool row_shape_init_ = false;
+    // set_dequant: shards hold packed 8-bit rows (row_shape_, dtype_ and
+    // row_bytes_ describe those), gathers return [n, dequant_dim_] rows
+    int64_t dequant_dim_ = 0;  // 0: ordinary store
+    torch::Dtype dequant_out_ = torch::kFloat32;
     // per-executing-device split/join events for the tier-split gather
     // (events must live on the device whose streams record them)
     mutable std::unordered_map<int, std::pair<hipEvent_t, hipEvent_t>>
@@ -1893,6 +1988,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
 
     py::class_<ShardTensor>(m, "ShardTensor")
         .def(py::init<int>())
+        .def("set_dequant", &ShardTensor::set_dequant, py::arg("dim"),
+             py::arg("out_dtype"),
+             "empty store only: shards hold packed 8-bit rows "
+             "(quiver.quantize_rows) and gathers return [n, dim] rows of "
+             "out_dtype (float32, bfloat16 or float16)")
         .def("append", &ShardTensor::append)
         .def("append_item", &ShardTensor::append_item)
         .def("append_from", &ShardTensor::append_from,

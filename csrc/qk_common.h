@@ -177,6 +177,21 @@ void launch_gather_reuse(hipStream_t s, const GatherSpec& spec,
                          const int64_t* n_dev, const int64_t* order,
                          int64_t order_n, const GatherReuse& ru);
 
+// Gather of 8-bit rows, dequantized on the way: a stored row is
+// spec.row_bytes = round_up(dim + 8, 16) bytes: dim uint8 codes q, zero
+// padding, and in the last 8 bytes scale (fp32) then lo (fp32).
+//   out[i, c] = round_to_nearest_even(fmaf(q[c], scale, lo))
+// out is [n, dim] of out_elem, rows packed (dim * sizeof(out_elem) bytes
+// apart).  Row selection, n_dev, order and skipped rows are those of
+// launch_gather.  Throws if spec.row_bytes does not match dim.
+enum class DequantElem { f32, bf16, f16 };
+void launch_gather_dequant(hipStream_t s, const GatherSpec& spec,
+                           const int64_t* indices, int64_t n, void* out,
+                           DequantElem out_elem, int64_t dim,
+                           const int64_t* n_dev = nullptr,
+                           const int64_t* order = nullptr,
+                           int64_t order_n = 0);
+
 // Scatter-style update used by the python layer for cache fill / tests:
 // shard-resident rows only.  dst row indices[i] <- src[i].
 void launch_scatter(hipStream_t s, const GatherSpec& spec,

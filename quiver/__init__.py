@@ -19,6 +19,7 @@ from . import multiprocessing  # noqa: F401  registers ForkingPickler reducers
 from . import nn  # model zoo (SAGE/GAT) — PyG-compatible layers
 from . import trace  # pipeline-stage tracing (QUIVER_TRACE=1)
 from .loader import TrainingPrefetcher
+from .quant import quantize_rows, dequantize_rows
 
 __version__ = "0.1.0"
 
@@ -29,5 +30,5 @@ __all__ = [
     "p2pCliqueTopo", "init_p2p", "getNcclId", "NcclComm",
     "RequestBatcher", "HybridSampler", "InferenceServer",
     "InferenceServer_Debug", "generate_neighbour_num", "nn",
-    "TrainingPrefetcher",
+    "TrainingPrefetcher", "quantize_rows", "dequantize_rows",
 ]

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _ext
+from .quant import packed_row_bytes, quantize_rows
 from .shard_tensor import ShardTensor, ShardTensorConfig
 from .trace import trace_scope
 from .utils import Topo, CSRTopo, hot_order, parse_size
@@ -55,6 +56,8 @@ class Feature(object):
         self.mmap_handle_ = None
         self.disk_map = None
         self.cpu_part = torch.zeros(0)
+        # (dim, out_dtype) of an int8 store (from_cpu_tensor(quantize=...))
+        self.dequant = None
         assert self.clique_device_symmetry_check(), (
             f"\n{self.topo.info()}\nDifferent p2p clique sizes")
 
@@ -68,19 +71,65 @@ class Feature(object):
         element_size = cpu_tensor.shape[1] * cpu_tensor.element_size()
         return cache_memory_budget // element_size
 
+    def _cache_rows(self, cpu_tensor, cache_memory_budget, packing):
+        """cal_size for a tensor that is still to be packed."""
+        if packing:
+            return cache_memory_budget // packed_row_bytes(cpu_tensor.size(1))
+        return self.cal_size(cpu_tensor, cache_memory_budget)
+
     def partition(self, cpu_tensor: torch.Tensor, cache_memory_budget: int):
         cache_size = self.cal_size(cpu_tensor, cache_memory_budget)
         return [cpu_tensor[:cache_size], cpu_tensor[cache_size:]]
 
+    def _new_shard_tensor(self):
+        return ShardTensor(self.rank, ShardTensorConfig({}),
+                           dequant=self.dequant)
+
+    def _set_quantize(self, cpu_tensor, quantize, out_dtype):
+        """Validate quantize/out_dtype and record the store's (dim,
+        out_dtype); returns whether rows are to be packed."""
+        if quantize is None:
+            if out_dtype is not None:
+                raise ValueError("out_dtype needs quantize='int8'")
+            return False
+        if quantize != "int8":
+            raise ValueError(f"quantize must be None or 'int8', "
+                             f"got {quantize!r}")
+        if self.mmap_handle_ is not None:
+            raise NotImplementedError(
+                "a store with a disk tier cannot be quantized")
+        if cpu_tensor.dim() != 2 or not cpu_tensor.is_floating_point():
+            raise ValueError("quantize='int8' needs a 2-D floating-point "
+                             "tensor")
+        if out_dtype is None:
+            out_dtype = cpu_tensor.dtype if cpu_tensor.dtype in (
+                torch.bfloat16, torch.float16) else torch.float32
+        if out_dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise ValueError("out_dtype must be float32, bfloat16 or "
+                             "float16")
+        self.dequant = (cpu_tensor.size(1), out_dtype)
+        return True
+
     def from_cpu_tensor(self, cpu_tensor: torch.Tensor,
-                        score: torch.Tensor = None):
+                        score: torch.Tensor = None, quantize=None,
+                        out_dtype=None):
         """Split a CPU tensor into hot cache(s) + pinned cold tier.
 
         score: optional per-node hotness used for cache placement instead
         of out-degree — pass the access probability from
         GraphSageSampler.sample_prob for probability-driven placement
         (reference cal_neighbor_prob, quiver_sample.cu:100-111).
+
+        quantize="int8": both tiers store 8-bit rows with a per-row scale
+        and offset (`quiver.quantize_rows`), and the gather kernel
+        dequantizes them, so lookups still return [n, dim] rows: of
+        out_dtype, which defaults to float32 for a float32 input and to
+        the input's dtype for bfloat16/float16.  Every element comes back
+        within half a quantization step, (max - min) / 510 of its row.
+        `device_cache_size` counts packed bytes, so the hot tier holds
+        more rows.  Not available with the disk tier.
         """
+        packing = self._set_quantize(cpu_tensor, quantize, out_dtype)
         if self.cache_policy == "device_replicate":
             cache_memory_budget = parse_size(self.device_cache_size)
             shuffle_ratio = 0.0
@@ -88,8 +137,8 @@ class Feature(object):
             clique0 = self.topo.cliques[0]
             cache_memory_budget = parse_size(self.device_cache_size) * len(clique0)
             shuffle_ratio = min(
-                1.0, self.cal_size(cpu_tensor, cache_memory_budget)
-                / cpu_tensor.size(0))
+                1.0, self._cache_rows(cpu_tensor, cache_memory_budget,
+                                      packing) / cpu_tensor.size(0))
 
         if self.csr_topo is not None:
             if self.csr_topo.feature_order is None:
@@ -99,13 +148,18 @@ class Feature(object):
             self.feature_order = self.csr_topo.feature_order.to(self.rank) \
                 if torch.cuda.is_available() else self.csr_topo.feature_order
 
+        if packing:
+            # after the hot-order permutation; from here on the tensor is
+            # the packed one, so budgets below count packed bytes
+            cpu_tensor = quantize_rows(cpu_tensor)
+
         cache_part, self.cpu_part = self.partition(cpu_tensor,
                                                    cache_memory_budget)
         self.cpu_part = self.cpu_part.clone()
 
         if cache_part.shape[0] > 0 and self.cache_policy == "device_replicate":
             for device in self.device_list:
-                shard_tensor = ShardTensor(self.rank, ShardTensorConfig({}))
+                shard_tensor = self._new_shard_tensor()
                 shard_tensor.append(cache_part, device)
                 self.device_tensor_list[device] = shard_tensor
         elif cache_part.shape[0] > 0:
@@ -120,7 +174,7 @@ class Feature(object):
                                  (cache_part.shape[0] +
                                   len(clique_devices) - 1)
                                  // len(clique_devices))
-                shard_tensor = ShardTensor(self.rank, ShardTensorConfig({}))
+                shard_tensor = self._new_shard_tensor()
                 cur_pos = 0
                 for idx, device in enumerate(clique_devices):
                     if idx == len(clique_devices) - 1:
@@ -134,21 +188,20 @@ class Feature(object):
         if self.cpu_part.numel() > 0:
             if self.cache_policy == "device_replicate":
                 shard_tensor = self.device_tensor_list.get(
-                    self.rank, None) or ShardTensor(self.rank,
-                                                    ShardTensorConfig({}))
+                    self.rank, None) or self._new_shard_tensor()
                 shard_tensor.append(self.cpu_part, -1)
                 self.device_tensor_list[self.rank] = shard_tensor
             else:
                 clique_id = self.topo.get_clique_id(self.rank)
                 shard_tensor = self.clique_tensor_list.get(
-                    clique_id, None) or ShardTensor(self.rank,
-                                                    ShardTensorConfig({}))
+                    clique_id, None) or self._new_shard_tensor()
                 shard_tensor.append(self.cpu_part, -1)
                 self.clique_tensor_list[clique_id] = shard_tensor
 
     def from_cpu_tensor_dist(self, cpu_tensor: torch.Tensor, world=None,
                              rank=None, all_gather_object=None,
-                             score: torch.Tensor = None):
+                             score: torch.Tensor = None, quantize=None,
+                             out_dtype=None):
         """Collaborative p2p_clique_replicate build, one process per GPU.
 
         Each torchrun rank hipMallocs ONLY its own device's hot shard and
@@ -168,9 +221,13 @@ class Feature(object):
 
         world/rank/all_gather_object default to the initialized
         torch.distributed process group.
+
+        quantize, out_dtype: as in from_cpu_tensor; every rank packs only
+        the slices it stores.
         """
         assert self.cache_policy == "p2p_clique_replicate", \
             "distributed build targets the sharded (p2p) layout"
+        packing = self._set_quantize(cpu_tensor, quantize, out_dtype)
         if all_gather_object is None:
             import torch.distributed as dist
             assert dist.is_initialized(), \
@@ -185,7 +242,7 @@ class Feature(object):
         assert world is not None and rank is not None
         budget = parse_size(self.device_cache_size)
         total_budget = budget * world
-        cache_rows = min(self.cal_size(cpu_tensor, total_budget),
+        cache_rows = min(self._cache_rows(cpu_tensor, total_budget, packing),
                          cpu_tensor.size(0))
         prev_order = None
         if self.csr_topo is not None:
@@ -200,16 +257,16 @@ class Feature(object):
         def rows(beg, end):
             """Rows [beg, end) of the (virtually) reordered tensor —
             gathered per-slice so the full reordered tensor is never
-            materialized."""
-            if prev_order is None:
-                return cpu_tensor[beg:end]
-            return cpu_tensor[prev_order[beg:end]]
+            materialized; packed when quantizing."""
+            part = cpu_tensor[beg:end] if prev_order is None \
+                else cpu_tensor[prev_order[beg:end]]
+            return quantize_rows(part) if packing else part
 
         # this rank's shard of the hot rows
         block = (cache_rows + world - 1) // world
         beg = min(rank * block, cache_rows)
         end = min(beg + block, cache_rows)
-        own = ShardTensor(self.rank, ShardTensorConfig({}))
+        own = self._new_shard_tensor()
         handles = []
         if end > beg:
             own.shard_tensor.append(rows(beg, end).contiguous(), self.rank)
@@ -226,7 +283,7 @@ class Feature(object):
         if len(devices) > 1:
             _ext.init_p2p(devices)
 
-        st = ShardTensor(self.rank, ShardTensorConfig({}))
+        st = self._new_shard_tensor()
         for r, dev, hs in sorted(gathered):
             if r == rank:
                 for i in range(own.shard_tensor.shard_count()):
@@ -243,12 +300,17 @@ class Feature(object):
         clique_id = self.topo.get_clique_id(self.rank)
         self.clique_tensor_list[clique_id] = st
 
-    def from_mmap(self, np_array, device_config: DeviceConfig):
+    def from_mmap(self, np_array, device_config: DeviceConfig,
+                  quantize=None):
         """Build from a (mmap) numpy array + explicit per-device partition.
 
         gpu_parts[device] is either a torch.Tensor of rows (np_array is None)
         or an index tensor selecting rows of np_array; cpu_part likewise.
+        quantize: not available here (the disk tier reads plain rows).
         """
+        if quantize is not None or self._quantized():
+            raise NotImplementedError(
+                "a quantized store cannot be built from a mmap")
         assert len(device_config.gpu_parts) == len(self.device_list)
 
         def load_part(part):
@@ -311,7 +373,17 @@ class Feature(object):
         self.feature_order = torch.zeros_like(local_range)
         self.feature_order[local_order.to(self.rank)] = local_range
 
+    def _quantized(self):
+        """Whether this is (or, before the lazy IPC init, will be) an
+        int8 store."""
+        return self.dequant is not None or (
+            self.ipc_handle_ is not None and len(self.ipc_handle_) > 6)
+
     def set_mmap_file(self, path, disk_map):
+        if self._quantized():
+            raise NotImplementedError(
+                "a quantized store has no disk tier: read_mmap returns "
+                "plain rows")
         self.lazy_init_from_ipc_handle()
         self.mmap_handle_ = np.load(path, mmap_mode="r")
         self.disk_map = disk_map.to(self.rank)
@@ -410,31 +482,44 @@ class Feature(object):
             for clique_id in self.clique_tensor_list:
                 gpu_ipc_handle_dict[clique_id] = \
                     self.clique_tensor_list[clique_id].share_ipc()[0]
-        return (gpu_ipc_handle_dict,
-                self.cpu_part if self.cpu_part.numel() > 0 else None,
-                self.device_list, self.device_cache_size, self.cache_policy,
-                self.csr_topo)
+        handle = (gpu_ipc_handle_dict,
+                  self.cpu_part if self.cpu_part.numel() > 0 else None,
+                  self.device_list, self.device_cache_size,
+                  self.cache_policy, self.csr_topo)
+        # a seventh field, (dim, out_dtype), only for an int8 store:
+        # handles of ordinary stores keep their six
+        if self.dequant is not None:
+            handle += (self.dequant,)
+        return handle
+
+    @staticmethod
+    def _unpack_ipc_handle(ipc_handle):
+        """The six fields of a handle plus its dequant field or None."""
+        if len(ipc_handle) not in (6, 7):
+            raise ValueError("Feature ipc handle: expected 6 or 7 fields")
+        return tuple(ipc_handle[:6]) + (
+            ipc_handle[6] if len(ipc_handle) == 7 else None,)
 
     def from_gpu_ipc_handle_dict(self, gpu_ipc_handle_dict, cpu_tensor):
         if self.cache_policy == "device_replicate":
-            handle = gpu_ipc_handle_dict.get(self.rank, []), cpu_tensor, \
-                self.rank
-            shard_tensor = ShardTensor.new_from_share_ipc(handle, self.rank)
-            self.device_tensor_list[self.rank] = shard_tensor
+            key = self.rank
+            tensor_list = self.device_tensor_list
         else:
-            clique_id = self.topo.get_clique_id(self.rank)
-            handle = gpu_ipc_handle_dict.get(clique_id, []), cpu_tensor, \
-                self.rank
-            shard_tensor = ShardTensor.new_from_share_ipc(handle, self.rank)
-            self.clique_tensor_list[clique_id] = shard_tensor
+            key = self.topo.get_clique_id(self.rank)
+            tensor_list = self.clique_tensor_list
+        handle = (gpu_ipc_handle_dict.get(key, []), cpu_tensor, self.rank)
+        if self.dequant is not None:
+            handle += (self.dequant,)
+        tensor_list[key] = ShardTensor.new_from_share_ipc(handle, self.rank)
         self.cpu_part = cpu_tensor if cpu_tensor is not None \
             else torch.zeros(0)
 
     @classmethod
     def new_from_ipc_handle(cls, rank, ipc_handle):
         (gpu_ipc_handle_dict, cpu_part, device_list, device_cache_size,
-         cache_policy, csr_topo) = ipc_handle
+         cache_policy, csr_topo, dequant) = cls._unpack_ipc_handle(ipc_handle)
         feature = cls(rank, device_list, device_cache_size, cache_policy)
+        feature.dequant = dequant
         feature.from_gpu_ipc_handle_dict(gpu_ipc_handle_dict, cpu_part)
         if csr_topo is not None:
             feature.feature_order = csr_topo.feature_order.to(rank)
@@ -444,7 +529,7 @@ class Feature(object):
     @classmethod
     def lazy_from_ipc_handle(cls, ipc_handle):
         (gpu_ipc_handle_dict, cpu_part, device_list, device_cache_size,
-         cache_policy, _) = ipc_handle
+         cache_policy, _, _) = cls._unpack_ipc_handle(ipc_handle)
         feature = cls(device_list[0], device_list, device_cache_size,
                       cache_policy)
         feature.ipc_handle = ipc_handle
@@ -455,7 +540,8 @@ class Feature(object):
             return
         self.rank = torch.cuda.current_device()
         (gpu_ipc_handle_dict, cpu_part, device_list, device_cache_size,
-         cache_policy, csr_topo) = self.ipc_handle
+         cache_policy, csr_topo, self.dequant) = \
+            self._unpack_ipc_handle(self.ipc_handle)
         self.from_gpu_ipc_handle_dict(gpu_ipc_handle_dict, cpu_part)
         self.csr_topo = csr_topo
         if csr_topo is not None:

@@ -34,8 +34,20 @@ class ShardTensorConfig:
 
 
 class ShardTensor:
-    def __init__(self, current_device: int, shard_tensor_config=None):
+    """dequant=(dim, out_dtype) makes a dequantizing store: its shards
+    are packed 8-bit rows (`quiver.quantize_rows`, uint8
+    [rows, round_up(dim + 8, 16)]) and every gather returns [n, dim] rows
+    of out_dtype; `shape` and `size` report [rows, dim].  The memory
+    budgets count packed bytes."""
+
+    def __init__(self, current_device: int, shard_tensor_config=None,
+                 dequant=None):
         self.shard_tensor = _ext.ShardTensor(current_device)
+        self.dequant = None
+        if dequant is not None:
+            dim, out_dtype = dequant
+            self.shard_tensor.set_dequant(int(dim), out_dtype)
+            self.dequant = (int(dim), out_dtype)
         self.current_device = current_device
         self.shard_tensor_config = shard_tensor_config or ShardTensorConfig({})
         self.cpu_tensor = None
@@ -108,8 +120,9 @@ class ShardTensor:
         place until two further reusing gathers have been issued (or
         `drop_reuse_sources()` was called).  `scatter_update` and
         `append` retire every earlier output as a source.  Has no effect
-        on stores without both tiers, under stream capture, or with
-        QUIVER_GATHER_REUSE=0 in the environment."""
+        on stores without both tiers, on dequantizing stores, under
+        stream capture, or with QUIVER_GATHER_REUSE=0 in the
+        environment."""
         if self._inaccessible_ranges():
             raise RuntimeError("gather_n: some shards need the cross-clique "
                                "pass; use __getitem__")
@@ -162,6 +175,8 @@ class ShardTensor:
         items = [it.share_ipc() for it in self.shard_tensor.share_ipc()]
         if self.cpu_tensor is not None:
             self.cpu_tensor.share_memory_()
+        if self.dequant is not None:  # a fourth field, only then
+            return items, self.cpu_tensor, self.current_device, self.dequant
         return items, self.cpu_tensor, self.current_device
 
     def from_ipc_handle(self, gpu_ipc_list, cpu_tensor):
@@ -173,7 +188,8 @@ class ShardTensor:
 
     @classmethod
     def new_from_share_ipc(cls, ipc_handles, current_device):
-        gpu_ipc_list, cpu_tensor, _ = ipc_handles
-        st = cls(current_device, ShardTensorConfig({}))
+        gpu_ipc_list, cpu_tensor = ipc_handles[:2]
+        dequant = ipc_handles[3] if len(ipc_handles) > 3 else None
+        st = cls(current_device, ShardTensorConfig({}), dequant=dequant)
         st.from_ipc_handle(gpu_ipc_list, cpu_tensor)
         return st
