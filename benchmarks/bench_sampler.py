@@ -42,12 +42,27 @@ def make_graph(nodes, edges, seed=0, max_deg=20_000):
     return torch.from_numpy(indptr), torch.from_numpy(indices)
 
 
-def bench(mode, shape, batch=1024, iters=50, warmup=5, device=0):
+def make_weights(edges, seed=1):
+    """fp32 edge weights, uniform in [0.5, 2)."""
+    rng = np.random.default_rng(seed)
+    w = rng.random(edges, dtype=np.float32)
+    w *= 1.5
+    w += 0.5
+    return torch.from_numpy(w)
+
+
+def bench(mode, shape, batch=1024, iters=50, warmup=5, device=0,
+          return_eid=False, edge_weight=False):
     cfg = SHAPES[shape]
     indptr, indices = make_graph(cfg["nodes"], cfg["edges"])
     topo = quiver.CSRTopo(indptr=indptr, indices=indices)
+    opts = {}
+    if return_eid:
+        opts["return_eid"] = True
+    if edge_weight:
+        opts["edge_weight"] = make_weights(indices.numel())
     sampler = quiver.GraphSageSampler(topo, cfg["fanout"], device=device,
-                                      mode=mode)
+                                      mode=mode, **opts)
     g = torch.Generator().manual_seed(7)
     batches = [torch.randint(0, cfg["train"], (batch,), generator=g)
                for _ in range(warmup + iters)]
@@ -64,7 +79,8 @@ def bench(mode, shape, batch=1024, iters=50, warmup=5, device=0):
         torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     return dict(mode=mode, shape=shape, seps=edges / dt,
-                ms_per_batch=dt / iters * 1000, batch=batch, iters=iters)
+                ms_per_batch=dt / iters * 1000, batch=batch, iters=iters,
+                return_eid=bool(return_eid), edge_weight=bool(edge_weight))
 
 
 if __name__ == "__main__":
@@ -74,11 +90,18 @@ if __name__ == "__main__":
     p.add_argument("--batch", type=int, default=1024)
     p.add_argument("--iters", type=int, default=50)
     p.add_argument("--cpu-iters", type=int, default=5)
+    p.add_argument("--return-eid", action="store_true",
+                   help="sample with return_eid=True (Adj.e_id filled)")
+    p.add_argument("--edge-weight", action="store_true",
+                   help="edge-weighted draws, fp32 weights uniform in "
+                        "[0.5, 2) from a fixed seed")
     args = p.parse_args()
     for shape in args.shapes.split(","):
         for mode in args.modes.split(","):
             if mode != "CPU" and not torch.cuda.is_available():
                 continue
             iters = args.cpu_iters if mode == "CPU" else args.iters
-            res = bench(mode, shape, batch=args.batch, iters=iters)
+            res = bench(mode, shape, batch=args.batch, iters=iters,
+                        return_eid=args.return_eid,
+                        edge_weight=args.edge_weight)
             print(json.dumps(res), flush=True)

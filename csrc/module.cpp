@@ -255,11 +255,43 @@ class GpuSampler {
 
     ~GpuSampler() {
         for (void* p : registered_) (void)hipHostUnregister(p);
+        // two samplers over one host buffer may both hold a registration
+        // of it; the second unregister then fails, harmlessly, and must
+        // not be left behind as the next launch's "last error"
+        if (!registered_.empty()) (void)hipGetLastError();
     }
 
     void set_seed(uint64_t seed) {
         rng_counter_.store(seed);
         write_rng(seed);
+    }
+
+    // Opt-in edge data.  `weight`: one fp32 per CSR slot (empty = uniform
+    // draws); placed like `indices` (HBM in DMA mode, pinned in UVA mode).
+    // `emit_eid`: the fused chain emits [3, m] edge tensors (src, dst, id)
+    // and sample_neighbor_eid is available; ids are mapped through the
+    // constructor's eid when it was given, else they are CSR slots.
+    void set_edge_options(torch::Tensor weight, bool emit_eid) {
+        DeviceScope g(device_);
+        emit_eid_ = emit_eid;
+        weight_ = torch::Tensor();
+        weight_dptr_ = nullptr;
+        if (!weight.defined() || weight.numel() == 0) return;
+        TORCH_CHECK(weight.dtype() == torch::kFloat32,
+                    "edge weights must be float32");
+        TORCH_CHECK(weight.numel() == indices_.numel(),
+                    "edge weights: one per CSR slot expected");
+        if (dma_) {
+            weight_ = weight.contiguous().to(
+                torch::Device(torch::kCUDA, device_));
+            weight_dptr_ = weight_.data_ptr<float>();
+        } else {
+            weight_ = weight.contiguous();
+            TORCH_CHECK(weight_.device().is_cpu(),
+                        "UVA mode expects CPU edge weights");
+            weight_dptr_ = (float*)register_host(
+                weight_.data_ptr(), weight_.numel() * sizeof(float));
+        }
     }
 
     std::tuple<torch::Tensor, torch::Tensor> sample_neighbor(
@@ -278,11 +310,34 @@ class GpuSampler {
         auto [prefix, total] = exclusive_scan_total(counts, stream);
         auto out = torch::empty({total}, opts);
         qk::launch_rng_bump(stream, rng_dev(stream));
-        qk::launch_sample(stream, indptr_.data_ptr<int64_t>(), indices_dptr_,
-                          nullptr, seeds.data_ptr<int64_t>(), n, k,
-                          prefix.data_ptr<int64_t>(), out.data_ptr<int64_t>(),
-                          nullptr, 0, rng_dev(stream));
+        draw(stream, seeds.data_ptr<int64_t>(), n, k,
+             prefix.data_ptr<int64_t>(), out.data_ptr<int64_t>(), nullptr, 0,
+             nullptr);
         return {out, counts};
+    }
+
+    // sample_neighbor plus the id of every drawn edge, aligned with `out`.
+    std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>
+    sample_neighbor_eid(int /*stream_id*/, torch::Tensor seeds, int k) {
+        DeviceScope g(device_);
+        auto stream = current_stream();
+        seeds = seeds.contiguous();
+        TORCH_CHECK(seeds.device().is_cuda(), "seeds must be on GPU");
+        int64_t n = seeds.numel();
+        auto opts =
+            torch::TensorOptions().dtype(torch::kInt64).device(seeds.device());
+        auto counts = torch::empty({n}, opts);
+        qk::launch_capped_degree(stream, indptr_.data_ptr<int64_t>(),
+                                 seeds.data_ptr<int64_t>(), n, k,
+                                 counts.data_ptr<int64_t>());
+        auto [prefix, total] = exclusive_scan_total(counts, stream);
+        auto out = torch::empty({total}, opts);
+        auto ids = torch::empty({total}, opts);
+        qk::launch_rng_bump(stream, rng_dev(stream));
+        draw(stream, seeds.data_ptr<int64_t>(), n, k,
+             prefix.data_ptr<int64_t>(), out.data_ptr<int64_t>(),
+             ids.data_ptr<int64_t>(), 0, nullptr);
+        return {out, counts, ids};
     }
 
     // Returns (frontier, row_idx, col_idx): frontier[0:n_seeds] == seeds.
@@ -348,7 +403,8 @@ class GpuSampler {
     // torch.stack copy on the consumer's critical path (the stack of two
     // ~1M-row hop buffers cost ~0.63 ms/step of main-stream time).
     // frontier[0:n_prev] == previous hop's frontier (seeds first), sizes
-    // already exact.
+    // already exact.  After set_edge_options(.., emit_eid = true) edges is
+    // [3, m]: edges[2] = id of the graph edge each column was drawn from.
     // Raw variant: returns UPPER-BOUND-sized per-hop tensors plus the
     // device-resident sizes vector [m_0, u_0, m_1, u_1, ...] WITHOUT any
     // host synchronization — callers chain the feature gather behind it
@@ -406,13 +462,18 @@ class GpuSampler {
                                       prefix.data_ptr<int64_t>(), n_ub + 1,
                                       sd + 2 * h);  // m_h
             auto out = torch::empty({m_ub}, opts);
+            // edges[0] = col (src local), edges[1] = row (dst local):
+            // the finished edge_index, written in place by the kernels;
+            // with ids on, a third row edges[2] = id of each edge, written
+            // by the draw itself (the reindex keeps the edge order)
+            auto edges = torch::empty({emit_eid_ ? 3 : 2, m_ub}, opts);
+            int64_t* colp = edges.data_ptr<int64_t>();
+            int64_t* rowp = colp + m_ub;
+            int64_t* idp = emit_eid_ ? rowp + m_ub : nullptr;
             const uint64_t salt = (uint64_t)(h + 1) * 0xD1B54A32D192ED03ULL;
-            qk::launch_sample(stream, indptr_.data_ptr<int64_t>(),
-                              indices_dptr_, nullptr,
-                              cur.data_ptr<int64_t>(), n_ub, k,
-                              prefix.data_ptr<int64_t>(),
-                              out.data_ptr<int64_t>(), nullptr, salt,
-                              rng_dev(stream), n_dev);
+            draw(stream, cur.data_ptr<int64_t>(), n_ub, k,
+                 prefix.data_ptr<int64_t>(), out.data_ptr<int64_t>(), idp,
+                 salt, n_dev);
 
             // reindex [cur ++ out] -> frontier + local col ids
             const int64_t total_ub = n_ub + m_ub;
@@ -449,11 +510,6 @@ class GpuSampler {
                 n_ub, out.data_ptr<int64_t>(), m_ub,
                 scanned.data_ptr<int64_t>(), flags.data_ptr<int64_t>(),
                 frontier.data_ptr<int64_t>(), n_dev, sd + 2 * h);
-            // edges[0] = col (src local), edges[1] = row (dst local):
-            // the finished edge_index, written in place by the kernels
-            auto edges = torch::empty({2, m_ub}, opts);
-            int64_t* colp = edges.data_ptr<int64_t>();
-            int64_t* rowp = colp + m_ub;
             qk::launch_lookup_local(stream, keys.data_ptr<int64_t>(),
                                     local.data_ptr<int32_t>(), capacity,
                                     out.data_ptr<int64_t>(), m_ub,
@@ -523,6 +579,22 @@ class GpuSampler {
         return register_host_chunked(p, bytes, registered_);
     }
 
+    // The one draw of every sampling path: uniform (launch_sample, as
+    // ever) unless edge weights were set.  out_eids may be null.
+    void draw(hipStream_t stream, const int64_t* seeds, int64_t n, int k,
+              const int64_t* prefix, int64_t* out, int64_t* out_eids,
+              uint64_t salt, const int64_t* n_dev) {
+        if (weight_dptr_)
+            qk::launch_sample_weighted(
+                stream, indptr_.data_ptr<int64_t>(), indices_dptr_,
+                weight_dptr_, eid_dptr_, seeds, n, k, prefix, out, out_eids,
+                salt, rng_dev(stream), n_dev);
+        else
+            qk::launch_sample(stream, indptr_.data_ptr<int64_t>(),
+                              indices_dptr_, eid_dptr_, seeds, n, k, prefix,
+                              out, out_eids, salt, rng_dev(stream), n_dev);
+    }
+
     // lazily-allocated device RNG word (int64 tensor reinterpreted)
     uint64_t* rng_dev(hipStream_t /*stream*/) {
         if (!rng_dev_.defined()) {
@@ -548,6 +620,9 @@ class GpuSampler {
     torch::Tensor indptr_, indices_, eid_;
     int64_t* indices_dptr_ = nullptr;
     int64_t* eid_dptr_ = nullptr;
+    bool emit_eid_ = false;
+    torch::Tensor weight_;
+    float* weight_dptr_ = nullptr;
     std::vector<void*> registered_;
     std::atomic<uint64_t> rng_counter_{0x853c49e6748fea9bULL};
     torch::Tensor rng_dev_;
@@ -567,13 +642,50 @@ class CpuSampler {
         node_count_ = indptr_.numel() - 1;
     }
 
+    // Opt-in edge data: `eid` maps a CSR slot to the edge id reported by
+    // sample_neighbor_eid (empty = the slot itself); `weight` is one fp32
+    // per CSR slot (empty = uniform draws).
+    void set_edge_options(torch::Tensor eid, torch::Tensor weight) {
+        eid_ = torch::Tensor();
+        weight_ = torch::Tensor();
+        if (eid.defined() && eid.numel() > 0) {
+            TORCH_CHECK(eid.device().is_cpu() && eid.dtype() == torch::kInt64
+                            && eid.numel() == indices_.numel(),
+                        "eid: one int64 per CSR slot expected");
+            eid_ = eid.contiguous();
+        }
+        if (weight.defined() && weight.numel() > 0) {
+            TORCH_CHECK(weight.device().is_cpu() &&
+                            weight.dtype() == torch::kFloat32 &&
+                            weight.numel() == indices_.numel(),
+                        "edge weights: one float32 per CSR slot expected");
+            weight_ = weight.contiguous();
+        }
+    }
+
     std::tuple<torch::Tensor, torch::Tensor> sample_neighbor(
         torch::Tensor seeds, int k) {
+        auto [out, counts, ids] = sample_impl(seeds, k, false);
+        return {out, counts};
+    }
+
+    // sample_neighbor plus the id of every drawn edge, aligned with `out`.
+    std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>
+    sample_neighbor_eid(torch::Tensor seeds, int k) {
+        return sample_impl(seeds, k, true);
+    }
+
+    std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> sample_impl(
+        torch::Tensor seeds, int k, bool want_ids) {
         seeds = seeds.contiguous().cpu();
         int64_t n = seeds.numel();
         const int64_t* sp = seeds.data_ptr<int64_t>();
         const int64_t* indptr = indptr_.data_ptr<int64_t>();
         const int64_t* indices = indices_.data_ptr<int64_t>();
+        const int64_t* eid = eid_.defined() ? eid_.data_ptr<int64_t>()
+                                            : nullptr;
+        const float* wp = weight_.defined() ? weight_.data_ptr<float>()
+                                            : nullptr;
         auto counts = torch::empty({n}, seeds.options());
         int64_t* cp = counts.data_ptr<int64_t>();
         at::parallel_for(0, n, 512, [&](int64_t b, int64_t e) {
@@ -586,15 +698,39 @@ class CpuSampler {
         for (int64_t i = 0; i < n; ++i) prefix[i + 1] = prefix[i] + cp[i];
         auto out = torch::empty({prefix[n]}, seeds.options());
         int64_t* op = out.data_ptr<int64_t>();
+        auto ids = torch::empty({want_ids ? prefix[n] : 0}, seeds.options());
+        int64_t* ip = want_ids ? ids.data_ptr<int64_t>() : nullptr;
         at::parallel_for(0, n, 64, [&](int64_t b, int64_t e) {
             thread_local std::mt19937_64 gen(std::random_device{}());
             std::vector<int64_t> slot;
+            std::vector<std::pair<double, int64_t>> race;
             for (int64_t i = b; i < e; ++i) {
                 int64_t v = sp[i], beg = indptr[v];
                 int64_t deg = indptr[v + 1] - beg;
                 int64_t* dst = op + prefix[i];
                 if (deg <= k) {
                     for (int64_t j = 0; j < deg; ++j) dst[j] = indices[beg + j];
+                    if (ip) {
+                        slot.resize(deg);
+                        for (int64_t j = 0; j < deg; ++j) slot[j] = j;
+                    }
+                } else if (wp) {
+                    // exponential race, the rule of weighted_sample_kernel:
+                    // key = -log(u) / w with u in (0, 1], the k smallest
+                    // (key, position) pairs win
+                    race.resize(deg);
+                    for (int64_t j = 0; j < deg; ++j) {
+                        double u = 1.0 - std::generate_canonical<double, 53>(
+                                             gen);
+                        race[j] = {-std::log(u) / (double)wp[beg + j], j};
+                    }
+                    std::nth_element(race.begin(), race.begin() + k,
+                                     race.end());
+                    slot.resize(k);
+                    for (int64_t j = 0; j < k; ++j) {
+                        slot[j] = race[j].second;
+                        dst[j] = indices[beg + slot[j]];
+                    }
                 } else if (k <= 256 && deg > 2 * (int64_t)k) {
                     // Floyd's uniform k-subset: O(k^2), degree-independent
                     slot.clear();
@@ -618,9 +754,17 @@ class CpuSampler {
                     for (int64_t j = 0; j < k; ++j)
                         dst[j] = indices[beg + slot[j]];
                 }
+                // every branch leaves the drawn row positions in `slot`
+                if (ip) {
+                    int64_t* idst = ip + prefix[i];
+                    for (size_t j = 0; j < slot.size(); ++j) {
+                        int64_t p = beg + slot[j];
+                        idst[j] = eid ? eid[p] : p;
+                    }
+                }
             }
         });
-        return {out, counts};
+        return {out, counts, ids};
     }
 
     std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> reindex_single(
@@ -664,7 +808,7 @@ class CpuSampler {
     int64_t edge_count() const { return indices_.numel(); }
 
   private:
-    torch::Tensor indptr_, indices_;
+    torch::Tensor indptr_, indices_, eid_, weight_;
     int64_t node_count_;
 };
 
@@ -1941,6 +2085,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     py::class_<GpuSampler>(m, "Quiver")
         .def("sample_neighbor", &GpuSampler::sample_neighbor,
              py::call_guard<py::gil_scoped_release>())
+        .def("sample_neighbor_eid", &GpuSampler::sample_neighbor_eid,
+             py::call_guard<py::gil_scoped_release>(),
+             "sample_neighbor plus the id of every drawn edge")
+        .def("set_edge_options", &GpuSampler::set_edge_options,
+             py::arg("weight"), py::arg("emit_eid"),
+             "CSR-ordered fp32 edge weights (empty: uniform) and whether "
+             "the fused chain emits edge ids")
         .def("sample_hops", &GpuSampler::sample_hops,
              py::call_guard<py::gil_scoped_release>(),
              "fused multi-hop sample+reindex, one sync per batch")
@@ -1969,6 +2120,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     py::class_<CpuSampler>(m, "CPUQuiver")
         .def("sample_neighbor", &CpuSampler::sample_neighbor,
              py::call_guard<py::gil_scoped_release>())
+        .def("sample_neighbor_eid", &CpuSampler::sample_neighbor_eid,
+             py::call_guard<py::gil_scoped_release>(),
+             "sample_neighbor plus the id of every drawn edge")
+        .def("set_edge_options", &CpuSampler::set_edge_options,
+             py::arg("eid"), py::arg("weight"))
         .def("reindex_single", &CpuSampler::reindex_single,
              py::call_guard<py::gil_scoped_release>())
         .def("node_count", &CpuSampler::node_count)

@@ -77,6 +77,20 @@ void launch_sample(hipStream_t s, const int64_t* indptr, const int64_t* indices,
                    const uint64_t* rng_dev = nullptr,
                    const int64_t* n_dev = nullptr);
 
+// Edge-weighted variant of launch_sample: a row longer than k yields k
+// distinct edges drawn without replacement by successive sampling in
+// proportion to weights[slot] (one fp32 per CSR slot, finite and > 0), in
+// unspecified order; a row of at most k edges is copied in CSR order.
+// Same subgroup layout, RNG stream and dynamic-count convention.
+void launch_sample_weighted(hipStream_t s, const int64_t* indptr,
+                            const int64_t* indices, const float* weights,
+                            const int64_t* eid_base, const int64_t* seeds,
+                            int64_t n, int k, const int64_t* prefix,
+                            int64_t* out_nbrs, int64_t* out_eids,
+                            uint64_t rng_seed,
+                            const uint64_t* rng_dev = nullptr,
+                            const int64_t* n_dev = nullptr);
+
 // *rng += golden-ratio step; the per-batch seed advance as a graph node
 // (a captured chain must advance the seed ON DEVICE each replay).
 void launch_rng_bump(hipStream_t s, uint64_t* rng);

@@ -139,6 +139,163 @@ sample_kernel(const int64_t* __restrict__ indptr,
     }
 }
 
+// ---- edge-weighted draw -------------------------------------------------
+//
+// k edges of a row without replacement, drawn by successive sampling
+// (first edge with probability w_i / W, the next from the rest in
+// proportion to its weight, ...), as an exponential race: position j gets
+// key_j = -log(u_j) / w_j and the k smallest keys win.  No prefix sums
+// over the weights, and fp32 keys stay exact enough for any weight ratio.
+//
+// A slot is (key bits << 32) | position: keys are non-negative floats, so
+// their bit patterns order like the values and one 64-bit compare orders
+// slots by key, ties by position.  All slots of a row are distinct.
+
+constexpr uint64_t kNoSlot = ~0ULL;
+
+__device__ __forceinline__ uint64_t race_slot(uint64_t base, int64_t j,
+                                              float w) {
+    uint64_t h = splitmix64(base + (uint64_t)j * 0x632be59bd9b4e019ULL);
+    float u = (float)((h >> 40) + 1) * 0x1p-24f;      // (0, 1]
+    float key = -logf(u) / w;
+    // clear the sign: u == 1 gives -0.0f
+    uint32_t bits = __float_as_uint(key) & 0x7fffffffu;
+    return ((uint64_t)bits << 32) | (uint32_t)j;
+}
+
+// LDS written by one lane of a subgroup and read by another: the lanes
+// share a wavefront, whose LDS operations complete in order, but the
+// compiler must not move the accesses across this point.
+__device__ __forceinline__ void subgroup_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+__device__ __forceinline__ uint64_t subgroup_max(uint64_t v) {
+    for (int off = SUB / 2; off > 0; off >>= 1) {
+        uint64_t o = __shfl_xor(v, off, SUB);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+constexpr int kAhead = 4;   // steps whose weights are loaded together
+
+// w[a] = row_w[j + a * SUB].  A position past the row's end reads the
+// row's last weight instead (deg >= 1; the value is never used): loads
+// without a branch around them let the compiler count them, so a step
+// waits for its own weights only, not for the ones requested ahead.
+__device__ __forceinline__ void load_weights(float (&w)[kAhead],
+                                             const float* __restrict__ row_w,
+                                             int64_t j, int64_t deg) {
+#pragma unroll
+    for (int a = 0; a < kAhead; ++a, j += SUB)
+        w[a] = row_w[j < deg ? j : deg - 1];
+}
+
+// Same layout as sample_kernel: one 16-lane subgroup per seed row, four
+// rows per wave, k slots of LDS per row.  Lane l owns slots l, l + 16, ...
+// and keeps the largest of them (and where it is) in registers, so an
+// insertion costs the owning lane one pass over its own k / 16 slots and
+// the subgroup one max-reduction for the new threshold.
+template <bool WITH_EID>
+__global__ void __launch_bounds__(BLOCK)
+weighted_sample_kernel(const int64_t* __restrict__ indptr,
+                       const int64_t* __restrict__ indices,
+                       const float* __restrict__ weights,
+                       const int64_t* __restrict__ eid_base,
+                       const int64_t* __restrict__ seeds, int64_t n, int k,
+                       const int64_t* __restrict__ prefix,
+                       int64_t* __restrict__ out_nbrs,
+                       int64_t* __restrict__ out_eids, uint64_t rng_seed,
+                       const uint64_t* __restrict__ rng_dev,
+                       const int64_t* __restrict__ n_dev) {
+    if (rng_dev) rng_seed += *rng_dev;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    uint64_t* slots = reinterpret_cast<uint64_t*>(smem);  // ROWS_PER_BLOCK * k
+
+    const int64_t nn = n_dev ? *n_dev : n;
+    const int sub_id = threadIdx.x / SUB;
+    const int lane = threadIdx.x % SUB;
+    // this subgroup's 16 bits of the wave's 64-bit ballot
+    const int ballot_shift = (threadIdx.x % kWaveSize) - lane;
+    int64_t row = (int64_t)blockIdx.x * ROWS_PER_BLOCK + sub_id;
+    const int64_t row_stride = (int64_t)gridDim.x * ROWS_PER_BLOCK;
+
+    for (; row < nn; row += row_stride) {
+        const int64_t v = seeds[row];
+        const int64_t beg = indptr[v];
+        const int64_t deg = indptr[v + 1] - beg;
+        const int64_t off = prefix[row];
+        const uint64_t base = rng_seed + (uint64_t)row * 0x9e3779b97f4a7c15ULL;
+        if (deg <= (int64_t)k) {
+            for (int64_t j = lane; j < deg; j += SUB) {
+                out_nbrs[off + j] = indices[beg + j];
+                if (WITH_EID)
+                    out_eids[off + j] = eid_base ? eid_base[beg + j] : beg + j;
+            }
+            continue;
+        }
+        uint64_t* slot = slots + sub_id * k;
+        // the first k positions fill the slots
+        uint64_t own_max = 0;       // largest of this lane's slots
+        int own_at = -1;            // and its index; -1: lane owns none
+        for (int i = lane; i < k; i += SUB) {
+            uint64_t s = race_slot(base, i, weights[beg + i]);
+            slot[i] = s;
+            if (own_at < 0 || s > own_max) { own_max = s; own_at = i; }
+        }
+        subgroup_lds_sync();
+        uint64_t thr = subgroup_max(own_max);   // largest kept slot
+        // One pass over the rest of the row, 16 positions a step.  A hub
+        // row is one subgroup's serial chain of steps, so what a step
+        // costs is the latency of its weight load: the weights of the
+        // next kAhead steps are requested before this group of kAhead
+        // steps is worked through.
+        float w_now[kAhead], w_next[kAhead];
+        load_weights(w_now, weights + beg, (int64_t)k + lane, deg);
+        for (int64_t j0 = k; j0 < deg; j0 += SUB * kAhead) {
+            load_weights(w_next, weights + beg, j0 + SUB * kAhead + lane,
+                         deg);
+#pragma unroll
+            for (int a = 0; a < kAhead; ++a) {
+                const int64_t j = j0 + a * SUB + lane;
+                if (j - lane >= deg) break;         // uniform: row is over
+                const uint64_t cand =
+                    j < deg ? race_slot(base, j, w_now[a]) : kNoSlot;
+                uint32_t hits = (uint32_t)(__ballot(cand < thr)
+                                           >> ballot_shift) & 0xffffu;
+                while (hits) {
+                    const int src = __builtin_ctz(hits);
+                    hits &= hits - 1;
+                    const uint64_t c = __shfl(cand, src, SUB);
+                    if (c >= thr) continue;  // an earlier insertion beat it
+                    // replace the largest slot; only its owner's maximum
+                    // moves
+                    if (own_at >= 0 && own_max == thr) {
+                        slot[own_at] = c;
+                        own_max = 0;
+                        for (int i = lane; i < k; i += SUB) {
+                            uint64_t s = slot[i];
+                            if (s >= own_max) { own_max = s; own_at = i; }
+                        }
+                    }
+                    subgroup_lds_sync();
+                    thr = subgroup_max(own_max);
+                }
+            }
+#pragma unroll
+            for (int a = 0; a < kAhead; ++a) w_now[a] = w_next[a];
+        }
+        subgroup_lds_sync();
+        for (int i = lane; i < k; i += SUB) {
+            const int64_t p = beg + (int64_t)(uint32_t)slot[i];
+            out_nbrs[off + i] = indices[p];
+            if (WITH_EID) out_eids[off + i] = eid_base ? eid_base[p] : p;
+        }
+    }
+}
+
 // One 16-lane subgroup per node; product-reduce over the subgroup with shfl.
 __global__ void cal_next_kernel(const int64_t* __restrict__ indptr,
                                 const int64_t* __restrict__ indices,
@@ -242,6 +399,33 @@ void launch_sample(hipStream_t s, const int64_t* indptr, const int64_t* indices,
                                                       seeds, n, k, prefix,
                                                       out_nbrs, nullptr,
                                                       rng_seed, rng_dev, n_dev);
+    QK_CHECK_HIP(hipGetLastError());
+}
+
+void launch_sample_weighted(hipStream_t s, const int64_t* indptr,
+                            const int64_t* indices, const float* weights,
+                            const int64_t* eid_base, const int64_t* seeds,
+                            int64_t n, int k, const int64_t* prefix,
+                            int64_t* out_nbrs, int64_t* out_eids,
+                            uint64_t rng_seed, const uint64_t* rng_dev,
+                            const int64_t* n_dev) {
+    if (n == 0) return;
+    if (k < 1) throw std::runtime_error("sample: fanout k must be >= 1");
+    if (!weights)
+        throw std::runtime_error("sample_weighted: no edge weights");
+    size_t lds = (size_t)ROWS_PER_BLOCK * k * sizeof(uint64_t);
+    if (lds > 160 * 1024)
+        throw std::runtime_error(
+            "sample_weighted: fanout too large for the LDS slots");
+    auto kern = out_eids ? weighted_sample_kernel<true>
+                         : weighted_sample_kernel<false>;
+    if (lds > 64 * 1024)
+        QK_CHECK_HIP(hipFuncSetAttribute(
+            reinterpret_cast<const void*>(kern),
+            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    kern<<<grid_for(n, ROWS_PER_BLOCK), BLOCK, lds, s>>>(
+        indptr, indices, weights, eid_base, seeds, n, k, prefix, out_nbrs,
+        out_eids, rng_seed, rng_dev, n_dev);
     QK_CHECK_HIP(hipGetLastError());
 }
 

@@ -333,6 +333,11 @@ class TrainingPrefetcher:
                     ptr = getattr(adj.edge_index, DST_PTR_ATTR, None)
                     if ptr is not None:
                         ptr.record_stream(cur)
+                    # edge ids (sampler's return_eid): a view of the same
+                    # edge buffer on the chain, a tensor of its own on the
+                    # per-hop path
+                    if adj.e_id.is_cuda:
+                        adj.e_id.record_stream(cur)
                 if x is not None:
                     x.record_stream(cur)
             # consumer launches the training step for this batch inside the

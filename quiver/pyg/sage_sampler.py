@@ -66,9 +66,19 @@ class GraphSageSampler:
         device: GPU id (ignored in CPU mode).
         mode: "UVA" (graph pinned in host DRAM, zero-copy sampled from the
             GPU), "GPU" (graph resident in HBM), or "CPU".
+        return_eid: fill every Adj.e_id with the int64 id of the graph
+            edge each edge_index column was drawn from.  Ids are COO
+            positions when the topo carries an `eid` (built from an
+            edge_index, or given one), else CSR slots.
+        edge_weight: float tensor [E] in that same id space.  A row longer
+            than the fanout then yields distinct edges drawn without
+            replacement by successive sampling, each draw in proportion to
+            the weights of the edges still in the row.  Weights must be
+            finite and strictly positive.
     """
 
-    def __init__(self, csr_topo: CSRTopo, sizes, device=0, mode="UVA"):
+    def __init__(self, csr_topo: CSRTopo, sizes, device=0, mode="UVA",
+                 return_eid=False, edge_weight=None):
         assert mode in ["UVA", "GPU", "CPU"], f"invalid mode: {mode}"
         self.csr_topo = csr_topo
         self.sizes = list(sizes)
@@ -76,40 +86,92 @@ class GraphSageSampler:
         self.quiver = None
         self.device = device
         self.ipc_handle_ = None
+        self.return_eid = bool(return_eid)
+        # weights in CSR order, fp32; None = uniform draws
+        self.w_csr_ = None if edge_weight is None else \
+            self._csr_weights(csr_topo, edge_weight)
         # optional: keep the frontier tail ascending (monotone gather/CSR
         # addresses).  Measured ~+8% on pure PCIe gathers but e2e-neutral
         # (the extra torch ops cost what the locality saves) — off by
         # default, flip on for cold-tier-dominated workloads.
         self.sort_frontier = False
 
+    @staticmethod
+    def _csr_weights(csr_topo, edge_weight):
+        """Validate per-edge weights and permute them to CSR order once."""
+        w = torch.as_tensor(edge_weight).detach().cpu()
+        if w.dim() != 1 or w.numel() != csr_topo.edge_count:
+            raise ValueError(
+                f"edge_weight must have shape [{csr_topo.edge_count}] (one "
+                f"weight per edge), got {tuple(w.shape)}")
+        if not w.is_floating_point():
+            raise ValueError("edge_weight must be a float tensor")
+        w = w.to(torch.float32)
+        if not bool(torch.isfinite(w).all()) or not bool((w > 0).all()):
+            raise ValueError(
+                "edge_weight must be finite and strictly positive (checked "
+                "as float32); an edge that must never be drawn has to be "
+                "removed from the graph instead of given weight 0")
+        if csr_topo.eid is not None:
+            w = w[csr_topo.eid]
+        return w.contiguous()
+
     def lazy_init_quiver(self):
         if self.quiver is not None:
             return
+        opts = self.return_eid or self.w_csr_ is not None
+        none = torch.zeros(0, dtype=torch.long)
+        # the id map travels to the engine only when ids are asked for, so
+        # the default keeps its memory footprint
+        eid = self.csr_topo.eid if self.return_eid else None
+        w = self.w_csr_ if self.w_csr_ is not None \
+            else torch.zeros(0, dtype=torch.float32)
         if self.mode == "CPU":
             self.device = "cpu"
             self.quiver = _ext.cpu_quiver_from_csr_array(
                 self.csr_topo.indptr, self.csr_topo.indices)
+            if opts:
+                self.quiver.set_edge_options(
+                    none if eid is None else eid, w)
         else:
             self.device = torch.cuda.current_device()
-            eid = torch.zeros(0, dtype=torch.long)
             self.quiver = _ext.device_quiver_from_csr_array(
-                self.csr_topo.indptr, self.csr_topo.indices, eid, self.device,
+                self.csr_topo.indptr, self.csr_topo.indices,
+                none if eid is None else eid, self.device,
                 self.mode != "UVA")
+            if opts:
+                self.quiver.set_edge_options(w, self.return_eid)
 
-    def sample_layer(self, batch, size):
+    def _sample_layer(self, batch, size, with_eid):
         self.lazy_init_quiver()
         if not isinstance(batch, torch.Tensor):
             batch = torch.tensor(batch, dtype=torch.long)
         n_id = batch.to(self.device, non_blocking=False)
         size = size if size != -1 else self.csr_topo.node_count
+        fn = self.quiver.sample_neighbor_eid if with_eid \
+            else self.quiver.sample_neighbor
         if self.mode in ("GPU", "UVA"):
-            out, cnt = self.quiver.sample_neighbor(0, n_id, size)
-        else:
-            out, cnt = self.quiver.sample_neighbor(n_id, size)
+            return fn(0, n_id, size)
+        return fn(n_id, size)
+
+    def sample_layer(self, batch, size):
+        out, cnt = self._sample_layer(batch, size, False)
         return out, cnt
+
+    def sample_layer_eid(self, batch, size):
+        """sample_layer plus the id of every drawn edge, aligned with the
+        neighbours: (out, cnt, e_id)."""
+        return self._sample_layer(batch, size, True)
 
     def reindex(self, inputs, outputs, counts):
         return self.quiver.reindex_single(inputs, outputs, counts)
+
+    def _split_edges(self, edges):
+        """(edge_index, e_id) from one hop's native edge tensor: [2, m], or
+        with ids on [3, m] = (src, dst, id).  Views, no copy."""
+        if self.return_eid:
+            return edges[:2], edges[2]
+        return edges, torch.tensor([])
 
     def sample(self, input_nodes):
         """Sample a k-hop computational graph rooted at `input_nodes`.
@@ -131,18 +193,23 @@ class GraphSageSampler:
             with trace_scope("sampler.sample_hops"):
                 hops = self.quiver.sample_hops_ptr(nodes, self.sizes)
             prev_n = nodes.size(0)
-            for frontier, edge_index, dst_ptr in hops:
-                _attach_dst_ptr(edge_index, dst_ptr)
-                # edge_index is emitted by the native chain as one [2, m]
+            for frontier, edges, dst_ptr in hops:
+                # edges is emitted by the native chain as one [2, m]
                 # tensor (edges[0]=src local, edges[1]=dst local): no
                 # stack copy here
+                edge_index, e_id = self._split_edges(edges)
+                _attach_dst_ptr(edge_index, dst_ptr)
                 adj_size = torch.LongTensor([frontier.size(0), prev_n])
-                adjs.append(Adj(edge_index, torch.tensor([]), adj_size))
+                adjs.append(Adj(edge_index, e_id, adj_size))
                 prev_n = frontier.size(0)
             return frontier, batch_size, adjs[::-1]
         for size in self.sizes:
+            e_id = torch.tensor([])
             with trace_scope("sampler.sample_layer"):
-                out, cnt = self.sample_layer(nodes, size)
+                if self.return_eid:
+                    out, cnt, e_id = self.sample_layer_eid(nodes, size)
+                else:
+                    out, cnt = self.sample_layer(nodes, size)
             with trace_scope("sampler.reindex"):
                 frontier, row_idx, col_idx = self.reindex(nodes, out, cnt)
             if self.sort_frontier:
@@ -160,7 +227,6 @@ class GraphSageSampler:
             row_idx, col_idx = col_idx, row_idx
             edge_index = torch.stack([row_idx, col_idx], dim=0)
             adj_size = torch.LongTensor([frontier.size(0), nodes.size(0)])
-            e_id = torch.tensor([])
             adjs.append(Adj(edge_index, e_id, adj_size))
             nodes = frontier
         return nodes, batch_size, adjs[::-1]
@@ -204,13 +270,12 @@ class GraphSageSampler:
             u = int(sizes_pin[2 * h + 1])
             frontier = f_ub[:u]
             # zero-copy: a narrowed view of the upper-bound edge buffer
-            edge_index = e_ub.narrow(1, 0, m)
+            edge_index, e_id = self._split_edges(e_ub.narrow(1, 0, m))
             if ptrs is not None:
                 # upper-bound-sized scan; its first prev + 1 entries are
                 # this hop's segment pointer
                 _attach_dst_ptr(edge_index, ptrs[h].narrow(0, 0, prev + 1))
-            adjs.append(Adj(edge_index, torch.tensor([]),
-                            torch.LongTensor([u, prev])))
+            adjs.append(Adj(edge_index, e_id, torch.LongTensor([u, prev])))
             prev = u
         return frontier, nodes.size(0), adjs[::-1]
 
@@ -236,12 +301,23 @@ class GraphSageSampler:
         return last_prob
 
     def share_ipc(self):
-        return self.csr_topo, self.sizes, self.mode
+        if not self.return_eid and self.w_csr_ is None:
+            return self.csr_topo, self.sizes, self.mode
+        if self.w_csr_ is not None:
+            self.w_csr_.share_memory_()
+        return (self.csr_topo, self.sizes, self.mode, self.return_eid,
+                self.w_csr_)
 
     @classmethod
     def lazy_from_ipc_handle(cls, ipc_handle):
-        csr_topo, sizes, mode = ipc_handle
-        return cls(csr_topo, sizes, _FakeDevice, mode)
+        csr_topo, sizes, mode = ipc_handle[:3]
+        return_eid, w_csr = ipc_handle[3:] if len(ipc_handle) > 3 \
+            else (False, None)
+        sampler = cls(csr_topo, sizes, _FakeDevice, mode,
+                      return_eid=return_eid)
+        # validated and permuted to CSR order by the sharing process
+        sampler.w_csr_ = w_csr
+        return sampler
 
 
 class SampleJob(Generic[T_co]):
@@ -279,9 +355,15 @@ class MixedGraphSageSampler:
     """
 
     def __init__(self, sample_job: SampleJob, num_workers, csr_topo: CSRTopo,
-                 sizes, device=0, mode="UVA_CPU_MIXED"):
+                 sizes, device=0, mode="UVA_CPU_MIXED", return_eid=False,
+                 edge_weight=None):
         assert mode in ["UVA_CPU_MIXED", "GPU_CPU_MIXED", "UVA_ONLY",
                         "GPU_ONLY"], f"invalid mode: {mode}"
+        # return_eid / edge_weight: as GraphSageSampler, applied to the
+        # device sampler and the CPU sampler alike
+        self.return_eid = bool(return_eid)
+        self.w_csr_ = None if edge_weight is None else \
+            GraphSageSampler._csr_weights(csr_topo, edge_weight)
         self.sample_job = sample_job
         self.num_workers = num_workers
         self.csr_topo = csr_topo
@@ -300,10 +382,15 @@ class MixedGraphSageSampler:
             return
         dev_mode = "UVA" if self.mode.startswith("UVA") else "GPU"
         self.device_sampler = GraphSageSampler(self.csr_topo, self.sizes,
-                                               self.device, dev_mode)
+                                               self.device, dev_mode,
+                                               return_eid=self.return_eid)
+        # already validated and in CSR order
+        self.device_sampler.w_csr_ = self.w_csr_
         if self.mode.endswith("MIXED"):
             self.cpu_sampler = GraphSageSampler(self.csr_topo, self.sizes,
-                                                mode="CPU")
+                                                mode="CPU",
+                                                return_eid=self.return_eid)
+            self.cpu_sampler.w_csr_ = self.w_csr_
             ctx = mp.get_context("spawn")
             self.result_queue = ctx.Queue()
             for w in range(self.num_workers):
@@ -403,9 +490,17 @@ class MixedGraphSageSampler:
         self.inited = False
 
     def share_ipc(self):
-        return (self.sample_job, self.num_workers, self.csr_topo, self.sizes,
-                self.device, self.mode)
+        handle = (self.sample_job, self.num_workers, self.csr_topo,
+                  self.sizes, self.device, self.mode)
+        if not self.return_eid and self.w_csr_ is None:
+            return handle
+        if self.w_csr_ is not None:
+            self.w_csr_.share_memory_()
+        return handle + (self.return_eid, self.w_csr_)
 
     @classmethod
     def lazy_from_ipc_handle(cls, ipc_handle):
-        return cls(*ipc_handle)
+        sampler = cls(*ipc_handle[:6])
+        if len(ipc_handle) > 6:
+            sampler.return_eid, sampler.w_csr_ = ipc_handle[6:]
+        return sampler
