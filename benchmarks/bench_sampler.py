@@ -83,6 +83,74 @@ def bench(mode, shape, batch=1024, iters=50, warmup=5, device=0,
                 return_eid=bool(return_eid), edge_weight=bool(edge_weight))
 
 
+def _timed(fn, args_list, sync):
+    """ms per call of fn over args_list, ending in a device synchronise."""
+    t0 = time.perf_counter()
+    for a in args_list:
+        fn(a)
+    sync()
+    return (time.perf_counter() - t0) / len(args_list) * 1000
+
+
+def _stats(xs):
+    """median and spread of the repeats."""
+    return dict(median=float(np.median(xs)), min=float(np.min(xs)),
+                max=float(np.max(xs)))
+
+
+def bench_links(mode, shape, topo, batch=1024, num_neg=1, iters=30,
+                repeats=7, warmup=5, device=0):
+    """Link-prediction batches: sample_negative alone, torch.unique on a
+    batch's endpoints alone, sample_links end to end, and, as the
+    baseline, plain sample() on the link batches' own seed nodes.  Each
+    repeat times `iters` calls of each of the four in turn; reported are
+    the median and the min..max over the repeats, in ms per call."""
+    cfg = SHAPES[shape]
+    sampler = quiver.GraphSageSampler(topo, cfg["fanout"], device=device,
+                                      mode=mode)
+    dev = "cpu" if mode == "CPU" else f"cuda:{device}"
+    sync = (lambda: None) if mode == "CPU" else torch.cuda.synchronize
+    g = torch.Generator().manual_seed(7)
+    pos = []
+    for _ in range(iters):
+        src = torch.randint(0, cfg["train"], (batch,), generator=g)
+        at = topo.indptr[src] + (torch.randint(0, 1 << 40, (batch,),
+                                               generator=g)
+                                 % topo.degree[src].clamp(min=1))
+        pos.append(torch.stack([src, topo.indices[at]]).to(dev))
+    srcs = [p[0].contiguous() for p in pos]
+    # the seed sets and endpoint lists of these very batches
+    seeds, ends, not_ok = [], [], 0
+    for p, s in zip(pos, srcs):
+        b = sampler.sample_links(p, num_neg=num_neg)
+        seeds.append(b.n_id[:b.batch_size].clone())
+        ends.append(torch.cat([p[0], p[1], sampler.sample_negative(
+            s, num_neg)[0].reshape(-1)]))
+        not_ok += int((~b.neg_ok).sum())
+    parts = dict(
+        sample_negative=(lambda s: sampler.sample_negative(s, num_neg), srcs),
+        unique=(lambda e: torch.unique(e, return_inverse=True), ends),
+        sample_links=(lambda p: sampler.sample_links(p, num_neg=num_neg),
+                      pos),
+        sample=(sampler.sample, seeds))
+    for fn, args_list in parts.values():
+        _timed(fn, args_list[:warmup], sync)
+    ms = {k: [] for k in parts}
+    for _ in range(repeats):
+        for k, (fn, args_list) in parts.items():
+            ms[k].append(_timed(fn, args_list, sync))
+    res = dict(mode=mode, shape=shape, links=True, batch=batch,
+               num_neg=num_neg, iters=iters, repeats=repeats,
+               seed_nodes=float(np.mean([s.numel() for s in seeds])),
+               not_ok=not_ok)
+    for k, v in ms.items():
+        res[k + "_ms"] = _stats(v)
+    links = res["sample_links_ms"]["median"]
+    res["share_negative"] = res["sample_negative_ms"]["median"] / links
+    res["share_unique"] = res["unique_ms"]["median"] / links
+    return res
+
+
 if __name__ == "__main__":
     p = argparse.ArgumentParser()
     p.add_argument("--modes", default="UVA,GPU,CPU")
@@ -95,7 +163,28 @@ if __name__ == "__main__":
     p.add_argument("--edge-weight", action="store_true",
                    help="edge-weighted draws, fp32 weights uniform in "
                         "[0.5, 2) from a fixed seed")
+    p.add_argument("--links", action="store_true",
+                   help="time link-prediction batches (sample_negative, "
+                        "sample_links) beside plain sample()")
+    p.add_argument("--num-neg", type=int, default=1,
+                   help="negatives per positive edge with --links")
+    p.add_argument("--repeats", type=int, default=7,
+                   help="repeats of the timed window with --links")
     args = p.parse_args()
+    if args.links:
+        for shape in args.shapes.split(","):
+            cfg = SHAPES[shape]
+            indptr, indices = make_graph(cfg["nodes"], cfg["edges"])
+            topo = quiver.CSRTopo(indptr=indptr, indices=indices)
+            for mode in args.modes.split(","):
+                if mode != "CPU" and not torch.cuda.is_available():
+                    continue
+                iters = args.cpu_iters if mode == "CPU" else args.iters
+                print(json.dumps(bench_links(
+                    mode, shape, topo, batch=args.batch,
+                    num_neg=args.num_neg, iters=iters,
+                    repeats=args.repeats)), flush=True)
+        sys.exit(0)
     for shape in args.shapes.split(","):
         for mode in args.modes.split(","):
             if mode != "CPU" and not torch.cuda.is_available():

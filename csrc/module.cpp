@@ -340,6 +340,34 @@ class GpuSampler {
         return {out, counts, ids};
     }
 
+    // Negative tails for link prediction: (neg int64 [n, num_neg], ok bool
+    // [n, num_neg]), contract at launch_sample_negative.  All sizes are
+    // known on the host: no sync.
+    std::tuple<torch::Tensor, torch::Tensor> sample_negative(
+        torch::Tensor src, int num_neg, int max_tries) {
+        DeviceScope g(device_);
+        auto stream = current_stream();
+        TORCH_CHECK(src.dtype() == torch::kInt64, "src must be int64");
+        TORCH_CHECK(src.device().is_cuda() &&
+                        src.device().index() == device_,
+                    "src must be on the sampler's GPU");
+        TORCH_CHECK(src.dim() == 1 && src.is_contiguous(),
+                    "src must be a contiguous 1-D tensor");
+        TORCH_CHECK(num_neg >= 1, "num_neg must be >= 1");
+        TORCH_CHECK(max_tries >= 1, "max_tries must be >= 1");
+        int64_t n = src.numel();
+        auto neg = torch::empty({n, (int64_t)num_neg}, src.options());
+        auto ok = torch::empty({n, (int64_t)num_neg},
+                               src.options().dtype(torch::kBool));
+        qk::launch_rng_bump(stream, rng_dev(stream));
+        qk::launch_sample_negative(
+            stream, indptr_.data_ptr<int64_t>(), indices_dptr_,
+            src.data_ptr<int64_t>(), n, num_neg, node_count_, max_tries,
+            neg.data_ptr<int64_t>(), (uint8_t*)ok.data_ptr<bool>(), 0,
+            rng_dev(stream));
+        return {neg, ok};
+    }
+
     // Returns (frontier, row_idx, col_idx): frontier[0:n_seeds] == seeds.
     std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> reindex_single(
         torch::Tensor seeds, torch::Tensor nbrs, torch::Tensor counts) {
@@ -765,6 +793,52 @@ class CpuSampler {
             }
         });
         return {out, counts, ids};
+    }
+
+    // Negative tails for link prediction, the contract of
+    // launch_sample_negative: (neg int64 [n, num_neg], ok bool [n, num_neg]).
+    std::tuple<torch::Tensor, torch::Tensor> sample_negative(
+        torch::Tensor src, int num_neg, int max_tries) {
+        TORCH_CHECK(src.dtype() == torch::kInt64, "src must be int64");
+        TORCH_CHECK(src.device().is_cpu(), "src must be a CPU tensor");
+        TORCH_CHECK(src.dim() == 1 && src.is_contiguous(),
+                    "src must be a contiguous 1-D tensor");
+        TORCH_CHECK(num_neg >= 1, "num_neg must be >= 1");
+        TORCH_CHECK(max_tries >= 1, "max_tries must be >= 1");
+        TORCH_CHECK(node_count_ >= 1, "the graph has no nodes");
+        int64_t n = src.numel();
+        const int64_t* sp = src.data_ptr<int64_t>();
+        const int64_t* indptr = indptr_.data_ptr<int64_t>();
+        const int64_t* indices = indices_.data_ptr<int64_t>();
+        auto neg = torch::empty({n, (int64_t)num_neg}, src.options());
+        auto ok = torch::empty({n, (int64_t)num_neg},
+                               src.options().dtype(torch::kBool));
+        int64_t* np = neg.data_ptr<int64_t>();
+        bool* okp = ok.data_ptr<bool>();
+        at::parallel_for(0, n, 64, [&](int64_t b, int64_t e) {
+            thread_local std::mt19937_64 gen(std::random_device{}());
+            std::uniform_int_distribution<int64_t> any_node(0,
+                                                            node_count_ - 1);
+            for (int64_t i = b; i < e; ++i) {
+                const int64_t u = sp[i];
+                const bool known = u >= 0 && u < node_count_;
+                const int64_t* row = known ? indices + indptr[u] : nullptr;
+                const int64_t* row_end =
+                    known ? indices + indptr[u + 1] : nullptr;
+                for (int j = 0; j < num_neg; ++j) {
+                    int64_t cand = 0;
+                    bool accepted = false;
+                    for (int t = 0; t < max_tries && !accepted; ++t) {
+                        cand = any_node(gen);
+                        accepted = known && cand != u &&
+                                   std::find(row, row_end, cand) == row_end;
+                    }
+                    np[i * num_neg + j] = cand;
+                    okp[i * num_neg + j] = accepted;
+                }
+            }
+        });
+        return {neg, ok};
     }
 
     std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> reindex_single(
@@ -2092,6 +2166,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              py::arg("weight"), py::arg("emit_eid"),
              "CSR-ordered fp32 edge weights (empty: uniform) and whether "
              "the fused chain emits edge ids")
+        .def("sample_negative", &GpuSampler::sample_negative,
+             py::arg("src"), py::arg("num_neg"), py::arg("max_tries"),
+             py::call_guard<py::gil_scoped_release>(),
+             "num_neg uniform non-neighbour tails per source: (neg, ok); "
+             "ok = 0 where max_tries candidates were all rejected")
         .def("sample_hops", &GpuSampler::sample_hops,
              py::call_guard<py::gil_scoped_release>(),
              "fused multi-hop sample+reindex, one sync per batch")
@@ -2125,6 +2204,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              "sample_neighbor plus the id of every drawn edge")
         .def("set_edge_options", &CpuSampler::set_edge_options,
              py::arg("eid"), py::arg("weight"))
+        .def("sample_negative", &CpuSampler::sample_negative,
+             py::arg("src"), py::arg("num_neg"), py::arg("max_tries"),
+             py::call_guard<py::gil_scoped_release>(),
+             "num_neg uniform non-neighbour tails per source: (neg, ok); "
+             "ok = 0 where max_tries candidates were all rejected")
         .def("reindex_single", &CpuSampler::reindex_single,
              py::call_guard<py::gil_scoped_release>())
         .def("node_count", &CpuSampler::node_count)

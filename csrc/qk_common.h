@@ -91,6 +91,24 @@ void launch_sample_weighted(hipStream_t s, const int64_t* indptr,
                             const uint64_t* rng_dev = nullptr,
                             const int64_t* n_dev = nullptr);
 
+// Negative tails for link prediction: num_neg per row i (source u = src[i]).
+// A candidate is drawn uniformly from [0, node_count) and rejected if it is
+// u or occurs in u's out-row (a scan: rows are not sorted); a rejected one
+// is redrawn, up to max_tries candidates in all.  out_neg[i*num_neg + j] is
+// the first accepted candidate with out_ok = 1, or, when all were rejected,
+// the last one drawn with out_ok = 0 (in range, but maybe an edge or u).
+// A source outside [0, node_count) reads no row and gets out_ok = 0.
+// RNG keyed by (rng_seed (+ *rng_dev), row i, j, try), so a source repeated
+// in src draws independently.  Throws on num_neg, max_tries or node_count
+// < 1; same dynamic-count convention as above.
+void launch_sample_negative(hipStream_t s, const int64_t* indptr,
+                            const int64_t* indices, const int64_t* src,
+                            int64_t n, int num_neg, int64_t node_count,
+                            int max_tries, int64_t* out_neg, uint8_t* out_ok,
+                            uint64_t rng_seed,
+                            const uint64_t* rng_dev = nullptr,
+                            const int64_t* n_dev = nullptr);
+
 // *rng += golden-ratio step; the per-batch seed advance as a graph node
 // (a captured chain must advance the seed ON DEVICE each replay).
 void launch_rng_bump(hipStream_t s, uint64_t* rng);

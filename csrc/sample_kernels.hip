@@ -296,6 +296,143 @@ weighted_sample_kernel(const int64_t* __restrict__ indptr,
     }
 }
 
+// ---- negative tails for link prediction -----------------------------------
+
+// Uniform in [0, bound): the high 64 bits of h * bound, h the full 64-bit
+// hash.  Not bounded_rand: its (h >> 11) * bound is a 53-bit value times
+// the bound and overflows 64 bits once the bound exceeds 2048, and here the
+// bound is the node count.  The 128-bit product cannot overflow for any
+// bound, and its bias is bound / 2^64 (under 2^-24 up to 2^40 nodes).
+__device__ __forceinline__ int64_t mulhi_rand(uint64_t h, uint64_t bound) {
+    return (int64_t)__umul64hi(h, bound);
+}
+
+constexpr int kNegAhead = 4;   // 16-wide steps of a row loaded together
+
+// nb[a] = row[j + a * SUB], or -1 past the row's end (no candidate is
+// negative).  Past the end the load goes to `spare`, any readable device
+// address, instead of standing under a branch: the compiler can then count
+// the loads and wait for a group's own only, and in UVA mode no dead load
+// crosses PCIe (the row is host memory, `spare` is not).
+__device__ __forceinline__ void load_neighbours(
+    int64_t (&nb)[kNegAhead], const int64_t* __restrict__ row,
+    const int64_t* __restrict__ spare, int64_t j, int64_t deg) {
+#pragma unroll
+    for (int a = 0; a < kNegAhead; ++a, j += SUB) {
+        const int64_t v = *(j < deg ? row + j : spare);
+        nb[a] = j < deg ? v : -1;
+    }
+}
+
+// One 16-lane subgroup per positive edge (row), four rows per wave.  Lane l
+// owns negatives l, l + 16, ... of the row, sixteen at a time.  One round
+// scans the out-row of the source once, kNegAhead 16-wide steps a group:
+// every lane loads its neighbours of the group (and requests the next
+// group's before it works through this one: a hub row is one subgroup's
+// serial chain, and what a group costs is its load latency), then each
+// candidate still unhit is handed round by its owner and compared by all
+// lanes at once.  So a row is read once per round for up to 16 candidates
+// instead of once per candidate (in UVA mode the row comes over PCIe), and
+// the scan leaves early once every open lane has been hit.  A lane whose
+// candidate was hit, or is the source itself, redraws while it has tries
+// left; the subgroup goes another round while any lane is open.  Every
+// branch around a shuffle or ballot is uniform across the subgroup.  A hub
+// row costs deg / 64 groups a round on its one subgroup.
+__global__ void __launch_bounds__(BLOCK)
+negative_sample_kernel(const int64_t* __restrict__ indptr,
+                       const int64_t* __restrict__ indices,
+                       const int64_t* __restrict__ src, int64_t n, int num_neg,
+                       int64_t node_count, int max_tries,
+                       int64_t* __restrict__ out_neg,
+                       uint8_t* __restrict__ out_ok, uint64_t rng_seed,
+                       const uint64_t* __restrict__ rng_dev,
+                       const int64_t* __restrict__ n_dev) {
+    if (rng_dev) rng_seed += *rng_dev;
+    const int64_t nn = n_dev ? *n_dev : n;
+    const int sub_id = threadIdx.x / SUB;
+    const int lane = threadIdx.x % SUB;
+    // this subgroup's 16 bits of the wave's 64-bit ballot
+    const int ballot_shift = (threadIdx.x % kWaveSize) - lane;
+    int64_t row = (int64_t)blockIdx.x * ROWS_PER_BLOCK + sub_id;
+    const int64_t row_stride = (int64_t)gridDim.x * ROWS_PER_BLOCK;
+
+    for (; row < nn; row += row_stride) {
+        const int64_t u = src[row];
+        // a source outside the graph has no row to read: nothing it draws
+        // is accepted
+        const bool known = u >= 0 && u < node_count;
+        const int64_t beg = known ? indptr[u] : 0;
+        const int64_t deg = known ? indptr[u + 1] - beg : 0;
+        // RNG stream is keyed by ROW (not node id): a source repeated in
+        // src draws independently each time.
+        const uint64_t base = rng_seed + (uint64_t)row * 0x9e3779b97f4a7c15ULL;
+        for (int j0 = 0; j0 < num_neg; j0 += SUB) {
+            const int j = j0 + lane;
+            // (row, j) picks the stream, the try number the draw in it
+            const uint64_t key =
+                splitmix64(base + (uint64_t)j * 0x632be59bd9b4e019ULL);
+            int64_t cand = mulhi_rand(splitmix64(key), (uint64_t)node_count);
+            int tries = 1;              // candidates drawn so far
+            bool open = j < num_neg;    // still without an accepted tail
+            bool ok = false;
+            for (;;) {
+                bool hit = cand == u || !known;
+                int64_t now[kNegAhead], next[kNegAhead];
+                load_neighbours(now, indices + beg, indptr, lane, deg);
+                for (int64_t p0 = 0; p0 < deg; p0 += SUB * kNegAhead) {
+                    // leave once every open lane has been hit
+                    uint32_t unhit =
+                        (uint32_t)(__ballot(open && !hit) >> ballot_shift) &
+                        0xffffu;
+                    if (!unhit) break;                      // uniform
+                    load_neighbours(next, indices + beg, indptr,
+                                    p0 + SUB * kNegAhead + lane, deg);
+                    // each candidate still unhit against this group: its
+                    // owner hands it round, every lane compares it with
+                    // its own neighbours
+                    while (unhit) {                         // uniform
+                        const int owner = __builtin_ctz(unhit);
+                        unhit &= unhit - 1;
+                        const int64_t c = __shfl(cand, owner, SUB);
+                        bool found = false;
+#pragma unroll
+                        for (int a = 0; a < kNegAhead; ++a)
+                            found |= now[a] == c;
+                        const uint32_t any =
+                            (uint32_t)(__ballot(found) >> ballot_shift) &
+                            0xffffu;
+                        if (any && lane == owner) hit = true;
+                    }
+#pragma unroll
+                    for (int a = 0; a < kNegAhead; ++a) now[a] = next[a];
+                }
+                if (open) {
+                    if (!hit) {
+                        ok = true;
+                        open = false;
+                    } else if (tries < max_tries) {
+                        cand = mulhi_rand(
+                            splitmix64(key + (uint64_t)tries *
+                                                 0x9e3779b97f4a7c15ULL),
+                            (uint64_t)node_count);
+                        ++tries;
+                    } else {
+                        open = false;   // keeps the last candidate, ok = 0
+                    }
+                }
+                const uint32_t any_open =
+                    (uint32_t)(__ballot(open) >> ballot_shift) & 0xffffu;
+                if (!any_open) break;                       // uniform
+            }
+            if (j < num_neg) {
+                const int64_t at = row * num_neg + j;
+                out_neg[at] = cand;
+                out_ok[at] = ok ? 1 : 0;
+            }
+        }
+    }
+}
+
 // One 16-lane subgroup per node; product-reduce over the subgroup with shfl.
 __global__ void cal_next_kernel(const int64_t* __restrict__ indptr,
                                 const int64_t* __restrict__ indices,
@@ -426,6 +563,25 @@ void launch_sample_weighted(hipStream_t s, const int64_t* indptr,
     kern<<<grid_for(n, ROWS_PER_BLOCK), BLOCK, lds, s>>>(
         indptr, indices, weights, eid_base, seeds, n, k, prefix, out_nbrs,
         out_eids, rng_seed, rng_dev, n_dev);
+    QK_CHECK_HIP(hipGetLastError());
+}
+
+void launch_sample_negative(hipStream_t s, const int64_t* indptr,
+                            const int64_t* indices, const int64_t* src,
+                            int64_t n, int num_neg, int64_t node_count,
+                            int max_tries, int64_t* out_neg, uint8_t* out_ok,
+                            uint64_t rng_seed, const uint64_t* rng_dev,
+                            const int64_t* n_dev) {
+    if (num_neg < 1)
+        throw std::runtime_error("sample_negative: num_neg must be >= 1");
+    if (max_tries < 1)
+        throw std::runtime_error("sample_negative: max_tries must be >= 1");
+    if (node_count < 1)
+        throw std::runtime_error("sample_negative: the graph has no nodes");
+    if (n == 0) return;
+    negative_sample_kernel<<<grid_for(n, ROWS_PER_BLOCK), BLOCK, 0, s>>>(
+        indptr, indices, src, n, num_neg, node_count, max_tries, out_neg,
+        out_ok, rng_seed, rng_dev, n_dev);
     QK_CHECK_HIP(hipGetLastError());
 }
 

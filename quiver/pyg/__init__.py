@@ -1,3 +1,5 @@
-from .sage_sampler import GraphSageSampler, MixedGraphSageSampler, SampleJob, Adj
+from .sage_sampler import (GraphSageSampler, MixedGraphSageSampler, SampleJob,
+                           Adj, LinkBatch)
 
-__all__ = ["GraphSageSampler", "MixedGraphSageSampler", "SampleJob", "Adj"]
+__all__ = ["GraphSageSampler", "MixedGraphSageSampler", "SampleJob", "Adj",
+           "LinkBatch"]

@@ -21,7 +21,8 @@ from ..utils import CSRTopo
 T_co = TypeVar("T_co", covariant=True)
 T = TypeVar("T")
 
-__all__ = ["GraphSageSampler", "MixedGraphSageSampler", "SampleJob", "Adj"]
+__all__ = ["GraphSageSampler", "MixedGraphSageSampler", "SampleJob", "Adj",
+           "LinkBatch"]
 
 # attribute name, shared with quiver.nn and quiver.loader
 DST_PTR_ATTR = "_quiver_dst_ptr"
@@ -45,6 +46,16 @@ class Adj(NamedTuple):
     def to(self, *args, **kwargs):
         return Adj(self.edge_index.to(*args, **kwargs),
                    self.e_id.to(*args, **kwargs), self.size)
+
+
+class LinkBatch(NamedTuple):
+    """What GraphSageSampler.sample_links returns."""
+    n_id: torch.Tensor              # as sample(): global ids, seeds first
+    batch_size: int                 # number of seed nodes
+    adjs: list                      # as sample()
+    edge_label_index: torch.Tensor  # int64 [2, P*(1+K)], LOCAL ids into n_id
+    edge_label: torch.Tensor        # float32 [P*(1+K)]: 1 for the first P
+    neg_ok: torch.Tensor            # bool [P*K]
 
 
 @dataclass(frozen=True)
@@ -230,6 +241,112 @@ class GraphSageSampler:
             adjs.append(Adj(edge_index, e_id, adj_size))
             nodes = frontier
         return nodes, batch_size, adjs[::-1]
+
+    def _check_ids(self, ids, name, shape):
+        """int64 node ids of the wanted rank; the id range is checked on a
+        CPU input only (on a GPU one it would cost a sync)."""
+        if ids.dtype != torch.int64:
+            raise ValueError(f"{name} must be int64, got {ids.dtype}")
+        if ids.dim() != len(shape) or any(
+                want is not None and got != want
+                for got, want in zip(ids.shape, shape)):
+            raise ValueError(f"{name} must have shape {shape} (None = any), "
+                             f"got {tuple(ids.shape)}")
+        if ids.device.type == "cpu" and ids.numel() > 0:
+            lo, hi = int(ids.min()), int(ids.max())
+            if lo < 0 or hi >= self.csr_topo.node_count:
+                raise ValueError(
+                    f"{name} holds ids outside [0, "
+                    f"{self.csr_topo.node_count}): min {lo}, max {hi}")
+
+    def sample_negative(self, src, num_neg=1, neg_tries=16):
+        """Draw `num_neg` negative tails for every source node in `src`.
+
+        A tail is drawn uniformly from all nodes and redrawn, up to
+        `neg_tries` candidates in all, while it is the source itself or
+        one of the source's out-neighbours (on a symmetrised graph that
+        covers both directions).  A source that occurs several times in
+        `src` draws independently each time.
+
+        Returns (neg int64 [P, num_neg], ok bool [P, num_neg]) on the
+        sampler's device.  ok == False marks a tail whose `neg_tries`
+        candidates were all rejected: the value is a valid node id but may
+        be a real edge or the source.
+        """
+        self.lazy_init_quiver()
+        if not isinstance(src, torch.Tensor):
+            src = torch.tensor(src, dtype=torch.long)
+        self._check_ids(src, "src", (None,))
+        if num_neg < 1 or neg_tries < 1:
+            raise ValueError("num_neg and neg_tries must be >= 1")
+        src = src.to(self.device).contiguous()
+        return self.quiver.sample_negative(src, int(num_neg), int(neg_tries))
+
+    def sample_links(self, edge_label_index, num_neg=1, neg_tries=16):
+        """One link-prediction batch: the positive edges given, `num_neg`
+        sampled negatives for each, and the k-hop computational graph of
+        all their endpoints.
+
+        Args:
+            edge_label_index: int64 [2, P] global ids (src row, dst row) of
+                the positive edges, a tensor or a (src, dst) pair.
+            num_neg: negative tails per positive edge, drawn with
+                :meth:`sample_negative` from the positive's source.  0
+                gives the positives only.
+            neg_tries: candidates per negative before it is given up.
+
+        Returns a LinkBatch.  `n_id`, `batch_size` and `adjs` are what
+        :meth:`sample` returns for the seed nodes, the distinct endpoints
+        of all positives and negatives.  `edge_label_index` holds LOCAL
+        ids into `n_id`: the P positives in input order, then the
+        negatives of edge 0, of edge 1, ..., each with its positive's
+        source as head.  `edge_label` is 1 for the positives and 0 after.
+
+        Two things are left to the caller:
+          (a) The positives' own edges may appear in `adjs`, the message
+              graph.  Who must exclude them builds the sampler with
+              return_eid=True and masks the hops by `Adj.e_id`.
+          (b) `neg_ok[i] == False` marks a negative whose `neg_tries`
+              candidates were all rejected; it may be a real edge, or the
+              source itself.  Mask the loss with `neg_ok` where that
+              matters (near-complete rows only).
+        """
+        self.lazy_init_quiver()
+        if not isinstance(edge_label_index, torch.Tensor):
+            if len(edge_label_index) != 2:
+                raise ValueError("edge_label_index must be [2, P] or a "
+                                 "(src, dst) pair")
+            edge_label_index = torch.stack(
+                [torch.as_tensor(e) for e in edge_label_index])
+        self._check_ids(edge_label_index, "edge_label_index", (2, None))
+        if num_neg < 0 or neg_tries < 1:
+            raise ValueError("num_neg must be >= 0 and neg_tries >= 1")
+        pos = edge_label_index.to(self.device)
+        src, dst = pos[0].contiguous(), pos[1]
+        p = src.numel()
+        if p == 0:
+            raise ValueError("edge_label_index holds no edge")
+        if num_neg > 0:
+            with trace_scope("sampler.sample_negative"):
+                neg, ok = self.quiver.sample_negative(src, int(num_neg),
+                                                      int(neg_tries))
+            ends = torch.cat([src, dst, neg.reshape(-1)])
+            neg_ok = ok.reshape(-1)
+        else:
+            ends = torch.cat([src, dst])
+            neg_ok = torch.zeros(0, dtype=torch.bool, device=ends.device)
+        # distinct endpoints as seeds: sample() keeps its seeds first and
+        # in order, so a seed's position is its local id
+        seeds, local = torch.unique(ends, return_inverse=True)
+        n_id, batch_size, adjs = self.sample(seeds)
+        head = torch.cat([local[:p],
+                          local[:p].repeat_interleave(int(num_neg))])
+        tail = local[p:]
+        label = torch.zeros(head.numel(), dtype=torch.float32,
+                            device=ends.device)
+        label[:p] = 1
+        return LinkBatch(n_id, batch_size, adjs, torch.stack([head, tail]),
+                         label, neg_ok)
 
     def sample_async(self, input_nodes):
         """Enqueue one full multi-hop sample with ZERO host syncs.
