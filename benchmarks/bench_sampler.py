@@ -151,6 +151,79 @@ def bench_links(mode, shape, topo, batch=1024, num_neg=1, iters=30,
     return res
 
 
+TIME_RANGE = 1 << 20
+
+
+def make_times(edges, seed=2):
+    """int64 edge times, uniform in [0, 2**20)."""
+    rng = np.random.default_rng(seed)
+    return torch.from_numpy(rng.integers(0, TIME_RANGE, edges,
+                                         dtype=np.int64))
+
+
+def bench_temporal(mode, shape, topo, edge_time, batch=1024, iters=30,
+                   repeats=7, warmup=5, device=0, links=False, num_neg=1):
+    """Temporal sampling: sample_temporal with every seed bounded at the
+    median edge time, beside two reference points on the same seeds from a
+    sampler without edge times: plain sample() (the fused chain, merged
+    frontier) and sample() with sort_frontier=True (the per-hop path that
+    sample_temporal is built like).  With `links` also temporal
+    sample_links beside the merged sample_links.  Each repeat times `iters`
+    calls of each in turn; reported are the median and the min..max over
+    the repeats, in ms per call."""
+    cfg = SHAPES[shape]
+    t0 = time.perf_counter()
+    temporal = quiver.GraphSageSampler(topo, cfg["fanout"], device=device,
+                                       mode=mode, edge_time=edge_time)
+    sort_s = time.perf_counter() - t0
+    plain = quiver.GraphSageSampler(topo, cfg["fanout"], device=device,
+                                    mode=mode)
+    per_hop = quiver.GraphSageSampler(topo, cfg["fanout"], device=device,
+                                      mode=mode)
+    per_hop.sort_frontier = True
+    dev = "cpu" if mode == "CPU" else f"cuda:{device}"
+    sync = (lambda: None) if mode == "CPU" else torch.cuda.synchronize
+    g = torch.Generator().manual_seed(7)
+    seeds = [torch.randint(0, cfg["train"], (batch,), generator=g).to(dev)
+             for _ in range(iters)]
+    median = TIME_RANGE // 2
+    bound = torch.full((batch,), median, dtype=torch.long, device=dev)
+    parts = dict(
+        sample_temporal=(lambda s: temporal.sample_temporal(s, bound), seeds),
+        sample=(plain.sample, seeds),
+        sample_per_hop=(per_hop.sample, seeds))
+    if links:
+        pos = []
+        for _ in range(iters):
+            src = torch.randint(0, cfg["train"], (batch,), generator=g)
+            at = topo.indptr[src] + (torch.randint(0, 1 << 40, (batch,),
+                                                   generator=g)
+                                     % topo.degree[src].clamp(min=1))
+            pos.append(torch.stack([src, topo.indices[at]]).to(dev))
+        parts["sample_links_temporal"] = (
+            lambda p: temporal.sample_links(p, num_neg=num_neg,
+                                            edge_label_time=bound), pos)
+        parts["sample_links"] = (
+            lambda p: plain.sample_links(p, num_neg=num_neg), pos)
+    sizes = {}
+    for k, (fn, args_list) in parts.items():
+        _timed(fn, args_list[:warmup], sync)
+        out = fn(args_list[0])
+        sizes[k] = dict(frontier=int(out[0].numel()),
+                        edges=int(sum(a.edge_index.shape[1]
+                                      for a in out[2])))
+    ms = {k: [] for k in parts}
+    for _ in range(repeats):
+        for k, (fn, args_list) in parts.items():
+            ms[k].append(_timed(fn, args_list, sync))
+    res = dict(mode=mode, shape=shape, temporal=True, links=bool(links),
+               batch=batch, num_neg=num_neg, iters=iters, repeats=repeats,
+               bound=median, sort_seconds=sort_s, first_batch=sizes)
+    for k, v in ms.items():
+        res[k + "_ms"] = _stats(v)
+    return res
+
+
 if __name__ == "__main__":
     p = argparse.ArgumentParser()
     p.add_argument("--modes", default="UVA,GPU,CPU")
@@ -169,8 +242,28 @@ if __name__ == "__main__":
     p.add_argument("--num-neg", type=int, default=1,
                    help="negatives per positive edge with --links")
     p.add_argument("--repeats", type=int, default=7,
-                   help="repeats of the timed window with --links")
+                   help="repeats of the timed window with --links and "
+                        "--temporal")
+    p.add_argument("--temporal", action="store_true",
+                   help="time sample_temporal (synthetic edge times, seeds "
+                        "bounded at the median) beside plain sample(); with "
+                        "--links also temporal sample_links")
     args = p.parse_args()
+    if args.temporal:
+        for shape in args.shapes.split(","):
+            cfg = SHAPES[shape]
+            indptr, indices = make_graph(cfg["nodes"], cfg["edges"])
+            topo = quiver.CSRTopo(indptr=indptr, indices=indices)
+            edge_time = make_times(indices.numel())
+            for mode in args.modes.split(","):
+                if mode != "CPU" and not torch.cuda.is_available():
+                    continue
+                iters = args.cpu_iters if mode == "CPU" else args.iters
+                print(json.dumps(bench_temporal(
+                    mode, shape, topo, edge_time, batch=args.batch,
+                    iters=iters, repeats=args.repeats, links=args.links,
+                    num_neg=args.num_neg)), flush=True)
+        sys.exit(0)
     if args.links:
         for shape in args.shapes.split(","):
             cfg = SHAPES[shape]

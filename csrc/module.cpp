@@ -368,6 +368,76 @@ class GpuSampler {
         return {neg, ok};
     }
 
+    // Opt-in edge times for sample_neighbor_temporal: one int64 per CSR
+    // slot, every row ascending (the caller built the engine from rows
+    // sorted by time); placed like `indices`.
+    void set_edge_time(torch::Tensor time_csr) {
+        DeviceScope g(device_);
+        TORCH_CHECK(time_csr.dtype() == torch::kInt64,
+                    "edge times must be int64");
+        TORCH_CHECK(time_csr.dim() == 1 &&
+                        time_csr.numel() == indices_.numel(),
+                    "edge times: one per CSR slot expected");
+        if (dma_) {
+            time_ = time_csr.contiguous().to(
+                torch::Device(torch::kCUDA, device_));
+            time_dptr_ = time_.data_ptr<int64_t>();
+        } else {
+            time_ = time_csr.contiguous();
+            TORCH_CHECK(time_.device().is_cpu(),
+                        "UVA mode expects CPU edge times");
+            // an empty graph has nothing to pin; the pointer is never read
+            time_dptr_ = time_.numel() == 0
+                ? indptr_.data_ptr<int64_t>()
+                : (int64_t*)register_host(
+                      time_.data_ptr(), time_.numel() * sizeof(int64_t));
+        }
+    }
+
+    // One hop of temporal sampling over composite keys root * node_count +
+    // node (contract at launch_sample_temporal): (out_keys, counts, eids),
+    // eids empty unless edge ids are emitted.  One host sync, for the total.
+    std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>
+    sample_neighbor_temporal(torch::Tensor keys, torch::Tensor seed_time,
+                             int k) {
+        DeviceScope g(device_);
+        auto stream = current_stream();
+        TORCH_CHECK(time_dptr_, "no edge times: call set_edge_time first");
+        for (const auto* t : {&keys, &seed_time}) {
+            const char* name = t == &keys ? "keys" : "seed_time";
+            TORCH_CHECK(t->dtype() == torch::kInt64, name, " must be int64");
+            TORCH_CHECK(t->device().is_cuda() &&
+                            t->device().index() == device_,
+                        name, " must be on the sampler's GPU");
+            TORCH_CHECK(t->dim() == 1 && t->is_contiguous(), name,
+                        " must be a contiguous 1-D tensor");
+        }
+        TORCH_CHECK(k >= 1 || k == -1, "k must be >= 1, or -1 for no cap");
+        int64_t n = keys.numel();
+        auto counts = torch::empty({n}, keys.options());
+        auto elig = torch::empty({n}, keys.options());
+        if (n == 0)
+            return {torch::empty({0}, keys.options()), counts,
+                    torch::empty({0}, keys.options())};
+        qk::launch_temporal_degree(
+            stream, indptr_.data_ptr<int64_t>(), time_dptr_,
+            keys.data_ptr<int64_t>(), n, node_count_,
+            seed_time.data_ptr<int64_t>(), seed_time.numel(), k,
+            elig.data_ptr<int64_t>(), counts.data_ptr<int64_t>());
+        auto [prefix, total] = exclusive_scan_total(counts, stream);
+        auto out = torch::empty({total}, keys.options());
+        auto ids = torch::empty({emit_eid_ ? total : 0}, keys.options());
+        qk::launch_rng_bump(stream, rng_dev(stream));
+        qk::launch_sample_temporal(
+            stream, indptr_.data_ptr<int64_t>(), indices_dptr_, eid_dptr_,
+            keys.data_ptr<int64_t>(), n, node_count_, k,
+            elig.data_ptr<int64_t>(), prefix.data_ptr<int64_t>(),
+            out.data_ptr<int64_t>(),
+            emit_eid_ ? ids.data_ptr<int64_t>() : nullptr, 0,
+            rng_dev(stream));
+        return {out, counts, ids};
+    }
+
     // Returns (frontier, row_idx, col_idx): frontier[0:n_seeds] == seeds.
     std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> reindex_single(
         torch::Tensor seeds, torch::Tensor nbrs, torch::Tensor counts) {
@@ -651,6 +721,8 @@ class GpuSampler {
     bool emit_eid_ = false;
     torch::Tensor weight_;
     float* weight_dptr_ = nullptr;
+    torch::Tensor time_;
+    int64_t* time_dptr_ = nullptr;
     std::vector<void*> registered_;
     std::atomic<uint64_t> rng_counter_{0x853c49e6748fea9bULL};
     torch::Tensor rng_dev_;
@@ -759,26 +831,8 @@ class CpuSampler {
                         slot[j] = race[j].second;
                         dst[j] = indices[beg + slot[j]];
                     }
-                } else if (k <= 256 && deg > 2 * (int64_t)k) {
-                    // Floyd's uniform k-subset: O(k^2), degree-independent
-                    slot.clear();
-                    for (int64_t j = deg - k; j < deg; ++j) {
-                        int64_t t = std::uniform_int_distribution<int64_t>(
-                            0, j)(gen);
-                        bool found = std::find(slot.begin(), slot.end(), t) !=
-                                     slot.end();
-                        slot.push_back(found ? j : t);
-                    }
-                    for (int64_t j = 0; j < k; ++j)
-                        dst[j] = indices[beg + slot[j]];
                 } else {
-                    slot.resize(k);
-                    for (int64_t j = 0; j < k; ++j) slot[j] = j;
-                    for (int64_t j = k; j < deg; ++j) {
-                        int64_t r = std::uniform_int_distribution<int64_t>(
-                            0, j)(gen);
-                        if (r < k) slot[r] = j;
-                    }
+                    uniform_subset(gen, deg, k, slot);
                     for (int64_t j = 0; j < k; ++j)
                         dst[j] = indices[beg + slot[j]];
                 }
@@ -789,6 +843,116 @@ class CpuSampler {
                         int64_t p = beg + slot[j];
                         idst[j] = eid ? eid[p] : p;
                     }
+                }
+            }
+        });
+        return {out, counts, ids};
+    }
+
+    // slot <- k distinct positions of [0, deg), deg > k, every k-subset
+    // equally likely.
+    template <typename Gen>
+    static void uniform_subset(Gen& gen, int64_t deg, int64_t k,
+                               std::vector<int64_t>& slot) {
+        if (k <= 256 && deg > 2 * k) {
+            // Floyd's uniform k-subset: O(k^2), degree-independent
+            slot.clear();
+            for (int64_t j = deg - k; j < deg; ++j) {
+                int64_t t = std::uniform_int_distribution<int64_t>(
+                    0, j)(gen);
+                bool found = std::find(slot.begin(), slot.end(), t) !=
+                             slot.end();
+                slot.push_back(found ? j : t);
+            }
+        } else {
+            slot.resize(k);
+            for (int64_t j = 0; j < k; ++j) slot[j] = j;
+            for (int64_t j = k; j < deg; ++j) {
+                int64_t r = std::uniform_int_distribution<int64_t>(
+                    0, j)(gen);
+                if (r < k) slot[r] = j;
+            }
+        }
+    }
+
+    // Opt-in edge times for sample_neighbor_temporal: one int64 per CSR
+    // slot, every row ascending.  `emit_eid`: sample_neighbor_temporal
+    // returns edge ids (this engine has no other switch for them).
+    void set_edge_time(torch::Tensor time_csr, bool emit_eid) {
+        emit_eid_ = emit_eid;
+        TORCH_CHECK(time_csr.device().is_cpu() &&
+                        time_csr.dtype() == torch::kInt64 &&
+                        time_csr.dim() == 1 &&
+                        time_csr.numel() == indices_.numel(),
+                    "edge times: one int64 per CSR slot expected");
+        time_ = time_csr.contiguous();
+    }
+
+    // One hop of temporal sampling, the contract of launch_sample_temporal:
+    // (out_keys, counts, eids), eids empty unless `emit_eid` was set.
+    std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>
+    sample_neighbor_temporal(torch::Tensor keys, torch::Tensor seed_time,
+                             int k) {
+        TORCH_CHECK(time_.defined(),
+                    "no edge times: call set_edge_time first");
+        for (const auto* t : {&keys, &seed_time}) {
+            const char* name = t == &keys ? "keys" : "seed_time";
+            TORCH_CHECK(t->dtype() == torch::kInt64, name, " must be int64");
+            TORCH_CHECK(t->device().is_cpu(), name, " must be a CPU tensor");
+            TORCH_CHECK(t->dim() == 1 && t->is_contiguous(), name,
+                        " must be a contiguous 1-D tensor");
+        }
+        TORCH_CHECK(k >= 1 || k == -1, "k must be >= 1, or -1 for no cap");
+        TORCH_CHECK(node_count_ >= 1, "the graph has no nodes");
+        const int64_t n = keys.numel(), roots = seed_time.numel();
+        const int64_t* kp = keys.data_ptr<int64_t>();
+        const int64_t* bp = seed_time.data_ptr<int64_t>();
+        const int64_t* indptr = indptr_.data_ptr<int64_t>();
+        const int64_t* indices = indices_.data_ptr<int64_t>();
+        const int64_t* tp = time_.data_ptr<int64_t>();
+        const int64_t* eid = eid_.defined() ? eid_.data_ptr<int64_t>()
+                                            : nullptr;
+        const bool want_ids = emit_eid_;
+        auto counts = torch::empty({n}, keys.options());
+        int64_t* cp = counts.data_ptr<int64_t>();
+        std::vector<int64_t> elig(n);
+        at::parallel_for(0, n, 512, [&](int64_t b, int64_t e) {
+            for (int64_t i = b; i < e; ++i) {
+                int64_t m = 0;
+                if (kp[i] >= 0 && kp[i] / node_count_ < roots) {
+                    const int64_t v = kp[i] % node_count_;
+                    const int64_t* row = tp + indptr[v];
+                    m = std::upper_bound(row, tp + indptr[v + 1],
+                                         bp[kp[i] / node_count_]) - row;
+                }
+                elig[i] = m;
+                cp[i] = (k >= 0 && m > k) ? k : m;
+            }
+        });
+        std::vector<int64_t> prefix(n + 1, 0);
+        for (int64_t i = 0; i < n; ++i) prefix[i + 1] = prefix[i] + cp[i];
+        auto out = torch::empty({prefix[n]}, keys.options());
+        int64_t* op = out.data_ptr<int64_t>();
+        auto ids = torch::empty({want_ids ? prefix[n] : 0}, keys.options());
+        int64_t* ip = want_ids ? ids.data_ptr<int64_t>() : nullptr;
+        at::parallel_for(0, n, 64, [&](int64_t b, int64_t e) {
+            thread_local std::mt19937_64 gen(std::random_device{}());
+            std::vector<int64_t> slot;
+            for (int64_t i = b; i < e; ++i) {
+                const int64_t m = elig[i];
+                if (m == 0) continue;
+                const int64_t beg = indptr[kp[i] % node_count_];
+                const int64_t tree = kp[i] - kp[i] % node_count_;
+                if (k < 0 || m <= k) {
+                    slot.resize(m);
+                    for (int64_t j = 0; j < m; ++j) slot[j] = j;
+                } else {
+                    uniform_subset(gen, m, k, slot);
+                }
+                for (size_t j = 0; j < slot.size(); ++j) {
+                    const int64_t p = beg + slot[j];
+                    op[prefix[i] + j] = tree + indices[p];
+                    if (ip) ip[prefix[i] + j] = eid ? eid[p] : p;
                 }
             }
         });
@@ -882,7 +1046,8 @@ class CpuSampler {
     int64_t edge_count() const { return indices_.numel(); }
 
   private:
-    torch::Tensor indptr_, indices_, eid_, weight_;
+    torch::Tensor indptr_, indices_, eid_, weight_, time_;
+    bool emit_eid_ = false;
     int64_t node_count_;
 };
 
@@ -2171,6 +2336,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              py::call_guard<py::gil_scoped_release>(),
              "num_neg uniform non-neighbour tails per source: (neg, ok); "
              "ok = 0 where max_tries candidates were all rejected")
+        .def("set_edge_time", &GpuSampler::set_edge_time,
+             py::arg("time_csr"),
+             "int64 edge times, one per CSR slot, every row ascending")
+        .def("sample_neighbor_temporal",
+             &GpuSampler::sample_neighbor_temporal, py::arg("keys"),
+             py::arg("seed_time"), py::arg("k"),
+             py::call_guard<py::gil_scoped_release>(),
+             "one hop over keys root * node_count + node, edges with time "
+             "<= seed_time[root] only: (out_keys, counts, eids)")
         .def("sample_hops", &GpuSampler::sample_hops,
              py::call_guard<py::gil_scoped_release>(),
              "fused multi-hop sample+reindex, one sync per batch")
@@ -2209,6 +2383,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              py::call_guard<py::gil_scoped_release>(),
              "num_neg uniform non-neighbour tails per source: (neg, ok); "
              "ok = 0 where max_tries candidates were all rejected")
+        .def("set_edge_time", &CpuSampler::set_edge_time,
+             py::arg("time_csr"), py::arg("emit_eid") = false,
+             "int64 edge times, one per CSR slot, every row ascending")
+        .def("sample_neighbor_temporal",
+             &CpuSampler::sample_neighbor_temporal, py::arg("keys"),
+             py::arg("seed_time"), py::arg("k"),
+             py::call_guard<py::gil_scoped_release>(),
+             "one hop over keys root * node_count + node, edges with time "
+             "<= seed_time[root] only: (out_keys, counts, eids)")
         .def("reindex_single", &CpuSampler::reindex_single,
              py::call_guard<py::gil_scoped_release>())
         .def("node_count", &CpuSampler::node_count)

@@ -109,6 +109,32 @@ void launch_sample_negative(hipStream_t s, const int64_t* indptr,
                             const uint64_t* rng_dev = nullptr,
                             const int64_t* n_dev = nullptr);
 
+// Temporal neighbour draw over rows sorted by edge time (ties in original
+// CSR order); time[slot] is one int64 per CSR slot.  A row i is a composite
+// key = root * node_count + v, and an edge of v is eligible iff its time <=
+// seed_time[root].
+//   launch_temporal_degree: elig[i] = eligible edges of v's row (binary
+//     search), capped[i] = min(elig[i], k); k == -1: no cap.  A negative key
+//     or a root >= n_roots gives 0.
+//   launch_sample_temporal: out_keys[prefix[i] .. + capped[i]) = root *
+//     node_count + neighbour; all elig[i] edges in time order when they are
+//     at most k, else k distinct ones, every k-subset equally likely, in
+//     unspecified order.  out_eids as in launch_sample.  The draw is exact
+//     for any row length.  RNG keyed by (rng_seed (+ *rng_dev), row, slot).
+//     Throws unless k >= 1 or k == -1.
+void launch_temporal_degree(hipStream_t s, const int64_t* indptr,
+                            const int64_t* time, const int64_t* keys,
+                            int64_t n, int64_t node_count,
+                            const int64_t* seed_time, int64_t n_roots, int k,
+                            int64_t* elig, int64_t* capped);
+void launch_sample_temporal(hipStream_t s, const int64_t* indptr,
+                            const int64_t* indices, const int64_t* eid_base,
+                            const int64_t* keys, int64_t n,
+                            int64_t node_count, int k, const int64_t* elig,
+                            const int64_t* prefix, int64_t* out_keys,
+                            int64_t* out_eids, uint64_t rng_seed,
+                            const uint64_t* rng_dev = nullptr);
+
 // *rng += golden-ratio step; the per-batch seed advance as a graph node
 // (a captured chain must advance the seed ON DEVICE each replay).
 void launch_rng_bump(hipStream_t s, uint64_t* rng);

@@ -433,6 +433,132 @@ negative_sample_kernel(const int64_t* __restrict__ indptr,
     }
 }
 
+// ---- temporal draw ----------------------------------------------------------
+//
+// Rows are sorted by edge time (ties in original CSR order), so the edges of
+// node v that exist by a bound are a prefix of its row.  A frontier entry is
+// a composite key = root * node_count + v: node v inside the tree of seed
+// `root`, whose bound seed_time[root] the whole tree inherits.
+
+// One thread per row: elig[row] = number of slots of v's row with time <=
+// bound (an upper_bound by binary search: O(log deg) dependent loads, which
+// in UVA mode cross PCIe, instead of a scan of the row), capped[row] =
+// min(elig, k), k < 0 meaning no cap.  A key that decodes to no node or to
+// no seed gets 0 and reads nothing.
+__global__ void temporal_degree_kernel(const int64_t* __restrict__ indptr,
+                                       const int64_t* __restrict__ time,
+                                       const int64_t* __restrict__ keys,
+                                       int64_t n, int64_t node_count,
+                                       const int64_t* __restrict__ seed_time,
+                                       int64_t n_roots, int k,
+                                       int64_t* __restrict__ elig,
+                                       int64_t* __restrict__ capped) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; i < n; i += stride) {
+        const int64_t key = keys[i];
+        int64_t m = 0;
+        if (key >= 0 && key / node_count < n_roots) {
+            const int64_t v = key % node_count;
+            const int64_t bound = seed_time[key / node_count];
+            const int64_t beg = indptr[v];
+            int64_t lo = beg, hi = indptr[v + 1];
+            while (lo < hi) {
+                const int64_t mid = lo + ((hi - lo) >> 1);
+                if (time[mid] <= bound) lo = mid + 1;
+                else hi = mid;
+            }
+            m = lo - beg;
+        }
+        elig[i] = m;
+        capped[i] = (k >= 0 && m > k) ? k : m;
+    }
+}
+
+// The layout and the three branches of sample_kernel, over the first
+// m = elig[row] slots of the row instead of all of it: m <= k (or no cap)
+// copies them in time order, Floyd's k-subset for k <= 128 and m > 2k, the
+// LDS atomicMax reservoir otherwise.  Draws are mulhi_rand on the full
+// hash, exact-range for any prefix length.  Every LDS hand-over between
+// lanes of the subgroup goes through subgroup_lds_sync(), the one at the
+// top of a draw included: the slots are reused from row to row.
+template <bool WITH_EID>
+__global__ void __launch_bounds__(BLOCK)
+temporal_sample_kernel(const int64_t* __restrict__ indptr,
+                       const int64_t* __restrict__ indices,
+                       const int64_t* __restrict__ eid_base,
+                       const int64_t* __restrict__ keys, int64_t n,
+                       int64_t node_count, int k,
+                       const int64_t* __restrict__ elig,
+                       const int64_t* __restrict__ prefix,
+                       int64_t* __restrict__ out_keys,
+                       int64_t* __restrict__ out_eids, uint64_t rng_seed,
+                       const uint64_t* __restrict__ rng_dev) {
+    if (rng_dev) rng_seed += *rng_dev;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int* slots = reinterpret_cast<int*>(smem);  // ROWS_PER_BLOCK * k
+
+    const int sub_id = threadIdx.x / SUB;
+    const int lane = threadIdx.x % SUB;
+    int64_t row = (int64_t)blockIdx.x * ROWS_PER_BLOCK + sub_id;
+    const int64_t row_stride = (int64_t)gridDim.x * ROWS_PER_BLOCK;
+
+    for (; row < n; row += row_stride) {
+        const int64_t m = elig[row];
+        if (m == 0) continue;           // also: a key that names no row
+        const int64_t key = keys[row];
+        const int64_t beg = indptr[key % node_count];
+        const int64_t tree = key - key % node_count;    // root * node_count
+        const int64_t off = prefix[row];
+        // RNG stream is keyed by ROW: the same node under two seeds, or a
+        // seed given twice, draws independently.
+        const uint64_t base = rng_seed + (uint64_t)row * 0x9e3779b97f4a7c15ULL;
+        if (k < 0 || m <= (int64_t)k) {
+            for (int64_t j = lane; j < m; j += SUB) {
+                out_keys[off + j] = tree + indices[beg + j];
+                if (WITH_EID)
+                    out_eids[off + j] = eid_base ? eid_base[beg + j] : beg + j;
+            }
+            continue;
+        }
+        int* slot = slots + sub_id * k;
+        subgroup_lds_sync();            // the previous row's reads are done
+        if (k <= 128 && m > 2 * (int64_t)k) {
+            // Floyd's uniform k-subset of [0, m): lane 0 draws
+            if (lane == 0) {
+                int c = 0;
+                for (int64_t j = m - k; j < m; ++j) {
+                    const uint64_t h = splitmix64(
+                        base + (uint64_t)j * 0x632be59bd9b4e019ULL);
+                    const int t = (int)mulhi_rand(h, (uint64_t)j + 1);
+                    bool found = false;
+                    for (int i = 0; i < c; ++i) {
+                        if (slot[i] == t) { found = true; break; }
+                    }
+                    slot[c++] = found ? (int)j : t;
+                }
+            }
+        } else {
+            // reservoir: position j replaces slot r = rand(j + 1) if r < k;
+            // the last writer of a slot is the largest j, hence atomicMax
+            for (int i = lane; i < k; i += SUB) slot[i] = i;
+            subgroup_lds_sync();
+            for (int64_t j = k + lane; j < m; j += SUB) {
+                const uint64_t h = splitmix64(
+                    base + (uint64_t)j * 0x632be59bd9b4e019ULL);
+                const int64_t r = mulhi_rand(h, (uint64_t)j + 1);
+                if (r < k) atomicMax(&slot[r], (int)j);
+            }
+        }
+        subgroup_lds_sync();
+        for (int i = lane; i < k; i += SUB) {
+            const int64_t p = beg + slot[i];
+            out_keys[off + i] = tree + indices[p];
+            if (WITH_EID) out_eids[off + i] = eid_base ? eid_base[p] : p;
+        }
+    }
+}
+
 // One 16-lane subgroup per node; product-reduce over the subgroup with shfl.
 __global__ void cal_next_kernel(const int64_t* __restrict__ indptr,
                                 const int64_t* __restrict__ indices,
@@ -582,6 +708,52 @@ void launch_sample_negative(hipStream_t s, const int64_t* indptr,
     negative_sample_kernel<<<grid_for(n, ROWS_PER_BLOCK), BLOCK, 0, s>>>(
         indptr, indices, src, n, num_neg, node_count, max_tries, out_neg,
         out_ok, rng_seed, rng_dev, n_dev);
+    QK_CHECK_HIP(hipGetLastError());
+}
+
+void launch_temporal_degree(hipStream_t s, const int64_t* indptr,
+                            const int64_t* time, const int64_t* keys,
+                            int64_t n, int64_t node_count,
+                            const int64_t* seed_time, int64_t n_roots, int k,
+                            int64_t* elig, int64_t* capped) {
+    if (!time)
+        throw std::runtime_error("sample_temporal: no edge times");
+    if (node_count < 1)
+        throw std::runtime_error("sample_temporal: the graph has no nodes");
+    if (n == 0) return;
+    temporal_degree_kernel<<<grid_for(n, BLOCK), BLOCK, 0, s>>>(
+        indptr, time, keys, n, node_count, seed_time, n_roots, k, elig,
+        capped);
+    QK_CHECK_HIP(hipGetLastError());
+}
+
+void launch_sample_temporal(hipStream_t s, const int64_t* indptr,
+                            const int64_t* indices, const int64_t* eid_base,
+                            const int64_t* keys, int64_t n,
+                            int64_t node_count, int k, const int64_t* elig,
+                            const int64_t* prefix, int64_t* out_keys,
+                            int64_t* out_eids, uint64_t rng_seed,
+                            const uint64_t* rng_dev) {
+    if (k < 1 && k != -1)
+        throw std::runtime_error(
+            "sample_temporal: fanout k must be >= 1, or -1 for no cap");
+    if (node_count < 1)
+        throw std::runtime_error("sample_temporal: the graph has no nodes");
+    if (n == 0) return;
+    // k == -1 copies every row: no slots
+    size_t lds = k < 0 ? 0 : (size_t)ROWS_PER_BLOCK * k * sizeof(int);
+    if (lds > 160 * 1024)
+        throw std::runtime_error(
+            "sample_temporal: fanout too large for LDS reservoir");
+    auto kern = out_eids ? temporal_sample_kernel<true>
+                         : temporal_sample_kernel<false>;
+    if (lds > 64 * 1024)
+        QK_CHECK_HIP(hipFuncSetAttribute(
+            reinterpret_cast<const void*>(kern),
+            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    kern<<<grid_for(n, ROWS_PER_BLOCK), BLOCK, lds, s>>>(
+        indptr, indices, eid_base, keys, n, node_count, k, elig, prefix,
+        out_keys, out_eids, rng_seed, rng_dev);
     QK_CHECK_HIP(hipGetLastError());
 }
 

@@ -5,7 +5,13 @@ dot-product decoder and binary cross-entropy over edge_label.
 
 Synthetic symmetrised graph with planted communities, so there is
 something to learn; swap in real data by loading your own edge_index and
-features.  The default size is small enough for --mode CPU."""
+features.  The default size is small enough for --mode CPU.
+
+--temporal gives every edge a synthetic time and trains on each positive
+with only the edges that existed before it: its endpoints and negatives
+root one tree each (sample_links(..., edge_label_time=t - 1)), so no
+message crosses an edge from the positive's future, nor the positive
+itself."""
 import argparse
 import os
 import sys
@@ -54,6 +60,9 @@ def main():
     p.add_argument("--batch", type=int, default=256)
     p.add_argument("--num-neg", type=int, default=2)
     p.add_argument("--steps", type=int, default=8)
+    p.add_argument("--temporal", action="store_true",
+                   help="synthetic edge times; sample each positive's "
+                        "message graph from the edges before it")
     args = p.parse_args()
 
     gen = torch.Generator().manual_seed(0)
@@ -65,7 +74,14 @@ def main():
                                        groups)
 
     dev = "cpu" if args.mode == "CPU" else "cuda:0"
-    sampler = quiver.GraphSageSampler(topo, [10, 5], device=0, mode=args.mode)
+    edge_time = None
+    if args.temporal:
+        # an edge and its reverse happen at the same moment
+        half = edge_index.shape[1] // 2
+        t = torch.randint(0, 1 << 20, (half,), generator=gen)
+        edge_time = torch.cat([t, t])
+    sampler = quiver.GraphSageSampler(topo, [10, 5], device=0, mode=args.mode,
+                                      edge_time=edge_time)
     if args.mode == "CPU":
         feature = x_cpu
     else:
@@ -81,8 +97,15 @@ def main():
     for step in range(args.steps):
         at = torch.randint(0, edge_index.shape[1], (args.batch,),
                            generator=gen)
-        batch = sampler.sample_links(edge_index[:, at],
-                                     num_neg=args.num_neg)
+        if args.temporal:
+            # t - 1: the bound is inclusive, and the positive (and its
+            # reverse) must stay out of its own message graph
+            batch = sampler.sample_links(edge_index[:, at],
+                                         num_neg=args.num_neg,
+                                         edge_label_time=edge_time[at] - 1)
+        else:
+            batch = sampler.sample_links(edge_index[:, at],
+                                         num_neg=args.num_neg)
         z = model(feature[batch.n_id], [adj.to(dev) for adj in batch.adjs])
         head, tail = batch.edge_label_index
         logit = (z[head] * z[tail]).sum(-1)

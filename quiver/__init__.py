@@ -6,7 +6,8 @@ wave64 HIP sampling/gather kernels, hipIpc + xGMI peer loads, RCCL
 collectives, zero-copy pinned-host tiers.
 """
 from .feature import Feature, DistFeature, PartitionInfo, DeviceConfig
-from .pyg import GraphSageSampler, MixedGraphSageSampler, SampleJob, LinkBatch
+from .pyg import (GraphSageSampler, MixedGraphSageSampler, SampleJob,
+                  LinkBatch, TemporalBatch)
 from .utils import CSRTopo
 from .utils import Topo as p2pCliqueTopo
 from .utils import init_p2p
@@ -26,6 +27,7 @@ __version__ = "0.1.0"
 __all__ = [
     "Feature", "DistFeature", "PartitionInfo", "DeviceConfig", "CSRTopo",
     "GraphSageSampler", "MixedGraphSageSampler", "SampleJob", "LinkBatch",
+    "TemporalBatch",
     "quiver_partition_feature", "load_quiver_feature_partition",
     "p2pCliqueTopo", "init_p2p", "getNcclId", "NcclComm",
     "RequestBatcher", "HybridSampler", "InferenceServer",

@@ -1,5 +1,5 @@
 from .sage_sampler import (GraphSageSampler, MixedGraphSageSampler, SampleJob,
-                           Adj, LinkBatch)
+                           Adj, LinkBatch, TemporalBatch)
 
 __all__ = ["GraphSageSampler", "MixedGraphSageSampler", "SampleJob", "Adj",
-           "LinkBatch"]
+           "LinkBatch", "TemporalBatch"]

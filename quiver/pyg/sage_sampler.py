@@ -22,7 +22,7 @@ T_co = TypeVar("T_co", covariant=True)
 T = TypeVar("T")
 
 __all__ = ["GraphSageSampler", "MixedGraphSageSampler", "SampleJob", "Adj",
-           "LinkBatch"]
+           "LinkBatch", "TemporalBatch"]
 
 # attribute name, shared with quiver.nn and quiver.loader
 DST_PTR_ATTR = "_quiver_dst_ptr"
@@ -58,6 +58,14 @@ class LinkBatch(NamedTuple):
     neg_ok: torch.Tensor            # bool [P*K]
 
 
+class TemporalBatch(NamedTuple):
+    """What GraphSageSampler.sample_temporal returns."""
+    n_id: torch.Tensor      # int64 global ids, the seeds first and in order
+    batch_size: int         # number of seeds (not deduplicated)
+    adjs: list              # as sample()
+    batch: torch.Tensor     # int64 [len(n_id)]: seed index of each entry's tree
+
+
 @dataclass(frozen=True)
 class _FakeDevice(object):
     pass
@@ -86,11 +94,23 @@ class GraphSageSampler:
             replacement by successive sampling, each draw in proportion to
             the weights of the edges still in the row.  Weights must be
             finite and strictly positive.
+        edge_time: int64 tensor [E] in that same id space; any int64 value
+            is allowed.  Enables :meth:`sample_temporal` and the
+            `edge_label_time` of :meth:`sample_links`.  The sampler keeps
+            its own time-sorted copy of the rows (8 B per edge for the
+            times, plus permuted copies of `indices` and of the id map
+            unless every row is already in time order); `csr_topo` is not
+            modified.  Every other method samples the same graph as
+            without it; a row returned whole comes in time order.  Not
+            combinable with `edge_weight`.
     """
 
     def __init__(self, csr_topo: CSRTopo, sizes, device=0, mode="UVA",
-                 return_eid=False, edge_weight=None):
+                 return_eid=False, edge_weight=None, edge_time=None):
         assert mode in ["UVA", "GPU", "CPU"], f"invalid mode: {mode}"
+        if edge_time is not None and edge_weight is not None:
+            raise ValueError("edge_time cannot be combined with edge_weight: "
+                             "there is no weighted temporal draw")
         self.csr_topo = csr_topo
         self.sizes = list(sizes)
         self.mode = mode
@@ -106,6 +126,36 @@ class GraphSageSampler:
         # (the extra torch ops cost what the locality saves) — off by
         # default, flip on for cold-tier-dominated workloads.
         self.sort_frontier = False
+        # (indices, times, id map or None), every row sorted by time; None =
+        # no edge times
+        self.temporal_ = None if edge_time is None else \
+            self._time_sorted(csr_topo, edge_time)
+
+    @staticmethod
+    def _time_sorted(csr_topo, edge_time):
+        """Validate per-edge times and sort every CSR row by them, stably.
+        Returns (indices, time, eid) in the sorted slot order; eid maps a
+        sorted slot to the id it reports (None: the slot itself).  Rows
+        already in time order pass the topo's own tensors through."""
+        t = torch.as_tensor(edge_time).detach().cpu()
+        if t.dim() != 1 or t.numel() != csr_topo.edge_count:
+            raise ValueError(
+                f"edge_time must have shape [{csr_topo.edge_count}] (one "
+                f"time per edge), got {tuple(t.shape)}")
+        if t.dtype != torch.int64:
+            raise ValueError(f"edge_time must be int64, got {t.dtype}")
+        if csr_topo.eid is not None:
+            t = t[csr_topo.eid]
+        t = t.contiguous()
+        row = torch.repeat_interleave(
+            torch.arange(csr_topo.node_count), csr_topo.degree)
+        if bool(((t[1:] >= t[:-1]) | (row[1:] != row[:-1])).all()):
+            return csr_topo.indices, t, csr_topo.eid
+        order = torch.argsort(t, stable=True)
+        perm = order[torch.argsort(row[order], stable=True)]
+        eid = perm if csr_topo.eid is None else csr_topo.eid[perm]
+        return (csr_topo.indices[perm].contiguous(), t[perm].contiguous(),
+                eid.contiguous())
 
     @staticmethod
     def _csr_weights(csr_topo, edge_weight):
@@ -134,24 +184,34 @@ class GraphSageSampler:
         none = torch.zeros(0, dtype=torch.long)
         # the id map travels to the engine only when ids are asked for, so
         # the default keeps its memory footprint
-        eid = self.csr_topo.eid if self.return_eid else None
+        indices, eid = self.csr_topo.indices, self.csr_topo.eid
+        if self.temporal_ is not None:
+            # the engine sees the time-sorted rows, and reports ids through
+            # the map that undoes the sort
+            indices, _, eid = self.temporal_
+        if not self.return_eid:
+            eid = None
         w = self.w_csr_ if self.w_csr_ is not None \
             else torch.zeros(0, dtype=torch.float32)
         if self.mode == "CPU":
             self.device = "cpu"
             self.quiver = _ext.cpu_quiver_from_csr_array(
-                self.csr_topo.indptr, self.csr_topo.indices)
+                self.csr_topo.indptr, indices)
             if opts:
                 self.quiver.set_edge_options(
                     none if eid is None else eid, w)
+            if self.temporal_ is not None:
+                self.quiver.set_edge_time(self.temporal_[1], self.return_eid)
         else:
             self.device = torch.cuda.current_device()
             self.quiver = _ext.device_quiver_from_csr_array(
-                self.csr_topo.indptr, self.csr_topo.indices,
+                self.csr_topo.indptr, indices,
                 none if eid is None else eid, self.device,
                 self.mode != "UVA")
             if opts:
                 self.quiver.set_edge_options(w, self.return_eid)
+            if self.temporal_ is not None:
+                self.quiver.set_edge_time(self.temporal_[1])
 
     def _sample_layer(self, batch, size, with_eid):
         self.lazy_init_quiver()
@@ -242,6 +302,67 @@ class GraphSageSampler:
             nodes = frontier
         return nodes, batch_size, adjs[::-1]
 
+    def sample_temporal(self, seeds, seed_time):
+        """Sample one k-hop tree per seed that holds only edges which
+        existed by the seed's time bound.
+
+        Args:
+            seeds: int64 [B] node ids; not deduplicated, a node given twice
+                roots two trees.
+            seed_time: int64 [B], CPU or GPU.  An edge e is eligible under
+                seed i iff edge_time[e] <= seed_time[i], at every hop of
+                the seed's tree.  Pass t - 1 to exclude an event at t.
+
+        A node with m eligible edges yields all of them, in ascending time
+        order (ties in CSR order), when m is at most the fanout, else
+        `fanout` distinct ones, every subset equally likely.  A fanout of
+        -1 takes all eligible edges.
+
+        Trees are disjoint: a node reached under two seeds appears twice in
+        `n_id`, once per seed; within one tree it appears once.  Returns
+        TemporalBatch(n_id, batch_size, adjs, batch): `n_id[:B] == seeds`,
+        `batch[j]` is the index of the seed whose tree holds `n_id[j]`,
+        `adjs` is laid out as :meth:`sample` returns it, both endpoints of
+        every edge in one tree.  Needs a sampler built with `edge_time`.
+        """
+        if self.temporal_ is None:
+            raise ValueError("sample_temporal needs a sampler built with "
+                             "edge_time")
+        self.lazy_init_quiver()
+        if not isinstance(seeds, torch.Tensor):
+            seeds = torch.tensor(seeds, dtype=torch.long)
+        self._check_ids(seeds, "seeds", (None,))
+        seed_time = torch.as_tensor(seed_time)
+        b = seeds.numel()
+        if seed_time.dtype != torch.int64 or tuple(seed_time.shape) != (b,):
+            raise ValueError(
+                f"seed_time must be int64 of shape [{b}] (one bound per "
+                f"seed), got {seed_time.dtype} {tuple(seed_time.shape)}")
+        n = self.csr_topo.node_count
+        if b * n >= 2 ** 62:
+            raise ValueError(f"{b} seeds on {n} nodes: the (seed, node) "
+                             "keys do not fit 62 bits")
+        seeds = seeds.to(self.device)
+        seed_time = seed_time.to(self.device).contiguous()
+        # node v in the tree of seed i is the key i * n + v: the frontier
+        # is deduplicated per tree by the ordinary reindex
+        keys = torch.arange(b, device=seeds.device) * n + seeds
+        adjs = []
+        for size in self.sizes:
+            with trace_scope("sampler.sample_layer"):
+                out, cnt, e_id = self.quiver.sample_neighbor_temporal(
+                    keys, seed_time, int(size))
+            with trace_scope("sampler.reindex"):
+                frontier, row_idx, col_idx = self.reindex(keys, out, cnt)
+            edge_index = torch.stack([col_idx, row_idx], dim=0)
+            adj_size = torch.LongTensor([frontier.size(0), keys.size(0)])
+            adjs.append(Adj(edge_index,
+                            e_id if self.return_eid else torch.tensor([]),
+                            adj_size))
+            keys = frontier
+        return TemporalBatch(keys % n, b, adjs[::-1],
+                             torch.div(keys, n, rounding_mode="floor"))
+
     def _check_ids(self, ids, name, shape):
         """int64 node ids of the wanted rank; the id range is checked on a
         CPU input only (on a GPU one it would cost a sync)."""
@@ -282,7 +403,8 @@ class GraphSageSampler:
         src = src.to(self.device).contiguous()
         return self.quiver.sample_negative(src, int(num_neg), int(neg_tries))
 
-    def sample_links(self, edge_label_index, num_neg=1, neg_tries=16):
+    def sample_links(self, edge_label_index, num_neg=1, neg_tries=16,
+                     edge_label_time=None):
         """One link-prediction batch: the positive edges given, `num_neg`
         sampled negatives for each, and the k-hop computational graph of
         all their endpoints.
@@ -294,6 +416,8 @@ class GraphSageSampler:
                 :meth:`sample_negative` from the positive's source.  0
                 gives the positives only.
             neg_tries: candidates per negative before it is given up.
+            edge_label_time: int64 [P], the time of every positive; needs a
+                sampler built with `edge_time`.  See "Temporal" below.
 
         Returns a LinkBatch.  `n_id`, `batch_size` and `adjs` are what
         :meth:`sample` returns for the seed nodes, the distinct endpoints
@@ -310,6 +434,18 @@ class GraphSageSampler:
               candidates were all rejected; it may be a real edge, or the
               source itself.  Mask the loss with `neg_ok` where that
               matters (near-complete rows only).
+
+        Temporal: with `edge_label_time` the endpoints are not merged.
+        The seeds are cat[src, dst, negatives], P * (2 + num_neg) of them,
+        each the root of its own tree through :meth:`sample_temporal` with
+        the time of its positive as bound (a negative inherits its
+        positive's), so `batch_size == P * (2 + num_neg)` and
+        `edge_label_index` holds seed positions: head i for positive i and
+        for its negatives, tails P + i and 2P + i * num_neg + j.  The
+        bound is inclusive: pass t - 1 to keep an event at t out of its
+        own message graph.  Negatives are still rejected against the
+        source's whole row, whatever the times of its edges: a tail that
+        becomes a neighbour only later is not drawn either.
         """
         self.lazy_init_quiver()
         if not isinstance(edge_label_index, torch.Tensor):
@@ -326,6 +462,16 @@ class GraphSageSampler:
         p = src.numel()
         if p == 0:
             raise ValueError("edge_label_index holds no edge")
+        if edge_label_time is not None:
+            if self.temporal_ is None:
+                raise ValueError("edge_label_time needs a sampler built "
+                                 "with edge_time")
+            t = torch.as_tensor(edge_label_time)
+            if t.dtype != torch.int64 or tuple(t.shape) != (p,):
+                raise ValueError(
+                    f"edge_label_time must be int64 of shape [{p}], got "
+                    f"{t.dtype} {tuple(t.shape)}")
+            t = t.to(self.device)
         if num_neg > 0:
             with trace_scope("sampler.sample_negative"):
                 neg, ok = self.quiver.sample_negative(src, int(num_neg),
@@ -335,10 +481,17 @@ class GraphSageSampler:
         else:
             ends = torch.cat([src, dst])
             neg_ok = torch.zeros(0, dtype=torch.bool, device=ends.device)
-        # distinct endpoints as seeds: sample() keeps its seeds first and
-        # in order, so a seed's position is its local id
-        seeds, local = torch.unique(ends, return_inverse=True)
-        n_id, batch_size, adjs = self.sample(seeds)
+        if edge_label_time is not None:
+            # every endpoint roots its own tree: a seed's position is its
+            # local id
+            n_id, batch_size, adjs, _ = self.sample_temporal(
+                ends, torch.cat([t, t, t.repeat_interleave(int(num_neg))]))
+            local = torch.arange(ends.numel(), device=ends.device)
+        else:
+            # distinct endpoints as seeds: sample() keeps its seeds first
+            # and in order, so a seed's position is its local id
+            seeds, local = torch.unique(ends, return_inverse=True)
+            n_id, batch_size, adjs = self.sample(seeds)
         head = torch.cat([local[:p],
                           local[:p].repeat_interleave(int(num_neg))])
         tail = local[p:]
@@ -418,6 +571,14 @@ class GraphSageSampler:
         return last_prob
 
     def share_ipc(self):
+        if self.temporal_ is not None:
+            # the time-sorted rows travel in shared memory: a worker does
+            # not sort again
+            for x in self.temporal_:
+                if x is not None:
+                    x.share_memory_()
+            return (self.csr_topo, self.sizes, self.mode, self.return_eid,
+                    None, self.temporal_)
         if not self.return_eid and self.w_csr_ is None:
             return self.csr_topo, self.sizes, self.mode
         if self.w_csr_ is not None:
@@ -428,12 +589,14 @@ class GraphSageSampler:
     @classmethod
     def lazy_from_ipc_handle(cls, ipc_handle):
         csr_topo, sizes, mode = ipc_handle[:3]
-        return_eid, w_csr = ipc_handle[3:] if len(ipc_handle) > 3 \
+        return_eid, w_csr = ipc_handle[3:5] if len(ipc_handle) > 3 \
             else (False, None)
         sampler = cls(csr_topo, sizes, _FakeDevice, mode,
                       return_eid=return_eid)
         # validated and permuted to CSR order by the sharing process
         sampler.w_csr_ = w_csr
+        if len(ipc_handle) > 5:
+            sampler.temporal_ = tuple(ipc_handle[5])
         return sampler
 
 
@@ -473,9 +636,12 @@ class MixedGraphSageSampler:
 
     def __init__(self, sample_job: SampleJob, num_workers, csr_topo: CSRTopo,
                  sizes, device=0, mode="UVA_CPU_MIXED", return_eid=False,
-                 edge_weight=None):
+                 edge_weight=None, edge_time=None):
         assert mode in ["UVA_CPU_MIXED", "GPU_CPU_MIXED", "UVA_ONLY",
                         "GPU_ONLY"], f"invalid mode: {mode}"
+        if edge_time is not None:
+            raise ValueError("MixedGraphSageSampler has no temporal "
+                             "sampling; use GraphSageSampler.sample_temporal")
         # return_eid / edge_weight: as GraphSageSampler, applied to the
         # device sampler and the CPU sampler alike
         self.return_eid = bool(return_eid)
