@@ -58,55 +58,31 @@ struct DeviceScope {
     ~DeviceScope() { (void)hipSetDevice(prev); }
 };
 
-// Chunked hipHostRegister for multi-GB UVA buffers (papers100M indices are
-// 12.5 GB): registering in 1 GB slices bounds the per-call pinning peak —
-// the reference's hard-won lesson (quiverRegister, quiver.cu.hpp:16-26).
-// Kernels need ONE contiguous device view, so the per-chunk device
-// pointers are verified contiguous; if the runtime ever maps them apart,
-// everything is unregistered and one whole-buffer registration is used
-// instead.  Returns the device-visible base pointer; appends every
-// registered host pointer to `registered` (for hipHostUnregister later).
-// Already-registered memory (e.g. a shared tensor registered by a prior
-// ShardTensor) is detected on the first chunk and reused.
-void* register_host_chunked(void* p, size_t bytes,
-                            std::vector<void*>& registered) {
-    constexpr size_t kChunk = 1ull << 30;
-    constexpr unsigned kFlags =
-        hipHostRegisterMapped | hipHostRegisterPortable;
-    auto devptr = [](void* hp) {
-        void* dp = nullptr;
-        QK_CHECK_HIP(hipHostGetDevicePointer(&dp, hp, 0));
-        return dp;
-    };
-    char* base = (char*)p;
-    std::vector<void*> regs;
-    void* dp0 = nullptr;
-    bool contiguous = true;
-    for (size_t off = 0; off < bytes; off += kChunk) {
-        size_t len = std::min(kChunk, bytes - off);
-        hipError_t err = hipHostRegister(base + off, len, kFlags);
-        if (err == hipErrorHostMemoryAlreadyRegistered && off == 0) {
-            (void)hipGetLastError();
-            return devptr(base);  // whole buffer registered by someone else
-        }
-        if (err != hipSuccess) {
-            for (void* r : regs) (void)hipHostUnregister(r);
-            (void)hipGetLastError();
-            QK_CHECK_HIP(err);  // throws with the error string
-        }
-        regs.push_back(base + off);
-        void* dp = devptr(base + off);
-        if (off == 0) dp0 = dp;
-        else if ((char*)dp != (char*)dp0 + off) contiguous = false;
-    }
-    if (!contiguous) {
-        for (void* r : regs) (void)hipHostUnregister(r);
-        QK_CHECK_HIP(hipHostRegister(p, bytes, kFlags));
-        registered.push_back(p);
-        return devptr(p);
-    }
-    registered.insert(registered.end(), regs.begin(), regs.end());
-    return dp0;
+// Host memory of the zero-copy (UVA) tiers: a contiguous CPU tensor as
+// pinned, device-mapped memory that kernels read over PCIe.  Pageable
+// memory cannot be pinned after the fact on every platform (virtualised
+// GPUs refuse hipHostRegister), so it is copied once into a hipHostMalloc
+// block owned by the returned tensor; a tensor that already lives in
+// pinned memory is returned as it is, which spares the copy.  Not torch's
+// pinned pool: it rounds a block up to a power of two, and papers100M
+// indices are 12.5 GB.
+torch::Tensor pin_host(const torch::Tensor& t) {
+    if (t.numel() == 0 || t.is_pinned()) return t;
+    void* p = nullptr;
+    QK_CHECK_HIP(hipHostMalloc(&p, t.nbytes(),
+                               hipHostMallocMapped | hipHostMallocPortable));
+    auto pinned = torch::from_blob(
+        p, t.sizes(), [](void* q) { (void)hipHostFree(q); }, t.options());
+    pinned.copy_(t);
+    return pinned;
+}
+
+// Device-visible pointer of a pin_host tensor (null for an empty one).
+void* host_devptr(const torch::Tensor& t) {
+    void* dp = nullptr;
+    if (t.numel() > 0)
+        QK_CHECK_HIP(hipHostGetDevicePointer(&dp, t.data_ptr(), 0));
+    return dp;
 }
 
 // Persistent worker pool for the CPU-staged gather.  Spawning threads
@@ -240,25 +216,17 @@ class GpuSampler {
         } else {
             // ZERO_COPY: pin the host CSR columns and read them from kernels
             // over PCIe (UVA).  Keeps graphs larger than HBM samplable.
-            indices_ = indices.contiguous();
-            TORCH_CHECK(indices_.device().is_cpu(),
+            TORCH_CHECK(indices.device().is_cpu(),
                         "UVA mode expects CPU indices");
-            indices_dptr_ = (int64_t*)register_host(
-                indices_.data_ptr(), indices_.numel() * sizeof(int64_t));
+            indices_ = pin_host(indices.contiguous());
+            indices_dptr_ = (int64_t*)host_devptr(indices_);
             if (has_eid_) {
-                eid_ = eid.contiguous();
-                eid_dptr_ = (int64_t*)register_host(
-                    eid_.data_ptr(), eid_.numel() * sizeof(int64_t));
+                TORCH_CHECK(eid.device().is_cpu(),
+                            "UVA mode expects CPU edge ids");
+                eid_ = pin_host(eid.contiguous());
+                eid_dptr_ = (int64_t*)host_devptr(eid_);
             }
         }
-    }
-
-    ~GpuSampler() {
-        for (void* p : registered_) (void)hipHostUnregister(p);
-        // two samplers over one host buffer may both hold a registration
-        // of it; the second unregister then fails, harmlessly, and must
-        // not be left behind as the next launch's "last error"
-        if (!registered_.empty()) (void)hipGetLastError();
     }
 
     void set_seed(uint64_t seed) {
@@ -286,11 +254,10 @@ class GpuSampler {
                 torch::Device(torch::kCUDA, device_));
             weight_dptr_ = weight_.data_ptr<float>();
         } else {
-            weight_ = weight.contiguous();
-            TORCH_CHECK(weight_.device().is_cpu(),
+            TORCH_CHECK(weight.device().is_cpu(),
                         "UVA mode expects CPU edge weights");
-            weight_dptr_ = (float*)register_host(
-                weight_.data_ptr(), weight_.numel() * sizeof(float));
+            weight_ = pin_host(weight.contiguous());
+            weight_dptr_ = (float*)host_devptr(weight_);
         }
     }
 
@@ -383,14 +350,13 @@ class GpuSampler {
                 torch::Device(torch::kCUDA, device_));
             time_dptr_ = time_.data_ptr<int64_t>();
         } else {
-            time_ = time_csr.contiguous();
-            TORCH_CHECK(time_.device().is_cpu(),
+            TORCH_CHECK(time_csr.device().is_cpu(),
                         "UVA mode expects CPU edge times");
+            time_ = pin_host(time_csr.contiguous());
             // an empty graph has nothing to pin; the pointer is never read
             time_dptr_ = time_.numel() == 0
                 ? indptr_.data_ptr<int64_t>()
-                : (int64_t*)register_host(
-                      time_.data_ptr(), time_.numel() * sizeof(int64_t));
+                : (int64_t*)host_devptr(time_);
         }
     }
 
@@ -673,10 +639,6 @@ class GpuSampler {
     int device() const { return device_; }
 
   private:
-    void* register_host(void* p, size_t bytes) {
-        return register_host_chunked(p, bytes, registered_);
-    }
-
     // The one draw of every sampling path: uniform (launch_sample, as
     // ever) unless edge weights were set.  out_eids may be null.
     void draw(hipStream_t stream, const int64_t* seeds, int64_t n, int k,
@@ -723,7 +685,6 @@ class GpuSampler {
     float* weight_dptr_ = nullptr;
     torch::Tensor time_;
     int64_t* time_dptr_ = nullptr;
-    std::vector<void*> registered_;
     std::atomic<uint64_t> rng_counter_{0x853c49e6748fea9bULL};
     torch::Tensor rng_dev_;
 };
@@ -1060,8 +1021,7 @@ struct ShardItem {
     int device = -1;          // -1 == pinned host
     bool owned_hip = false;   // free with hipFree
     bool from_ipc = false;    // close with hipIpcCloseMemHandle
-    torch::Tensor keeper;     // keeps host/tensor storage alive
-    std::vector<void*> host_regs;  // hipHostUnregister on destruction
+    torch::Tensor keeper;     // the pinned host tier's rows (pin_host)
 };
 
 class ShardTensorItem {
@@ -1139,7 +1099,6 @@ class ShardTensor {
                 DeviceScope g(device_);
                 (void)hipIpcCloseMemHandle(s.dptr);
             }
-            for (void* r : s.host_regs) (void)hipHostUnregister(r);
         }
     }
 
@@ -1203,12 +1162,11 @@ class ShardTensor {
         } else {
             TORCH_CHECK(tensor.device().is_cpu(),
                         "host shard expects a CPU tensor");
-            // zero-copy pinned host tier: register the tensor's own memory
-            // (shared-memory friendly, 1 GB chunks) and read it from
-            // gather kernels.
-            item.dptr = register_host_chunked(tensor.data_ptr(), bytes,
-                                              item.host_regs);
-            item.keeper = tensor;
+            // zero-copy pinned host tier: the store's own pinned copy of
+            // the rows (the tensor itself when it is pinned already),
+            // read by the gather kernels.
+            item.keeper = pin_host(tensor);
+            item.dptr = host_devptr(item.keeper);
         }
         shards_.push_back(std::move(item));
     }
