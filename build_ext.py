@@ -22,10 +22,18 @@ KERNEL_SOURCES = [
     "reindex_kernels.hip",
     "gather_kernels.hip",
     "segment_kernels.hip",
+    "gatv2_kernels.hip",
     "wgrad_kernels.hip",
     "gemm_kernels.hip",
 ]
 TORCH_SOURCES = ["module.cpp"]
+HEADERS = ["qk_common.h", "segment_io.h"]
+# per-file extra flags.  gatv2: keep the compiler from pairing fp32 math
+# into packed two-wide instructions (scalar fp32 ops only).
+EXTRA_FLAGS = {
+    "gatv2_kernels.hip": ["-Xclang", "-target-feature",
+                          "-Xclang", "-packed-fp32-ops"],
+}
 OUT = os.path.join(ROOT, "torch_quiver.so")
 
 
@@ -41,7 +49,7 @@ def torch_paths():
 def needs_rebuild(src, obj):
     if not os.path.exists(obj):
         return True
-    dep = [src] + [os.path.join(CSRC, "qk_common.h")]
+    dep = [src] + [os.path.join(CSRC, h) for h in HEADERS]
     omt = os.path.getmtime(obj)
     return any(os.path.getmtime(d) > omt for d in dep)
 
@@ -74,7 +82,8 @@ def build(verbose=True):
         obj = os.path.join(BUILD, s.replace(".hip", ".o"))
         objs.append(obj)
         if needs_rebuild(src, obj):
-            jobs.append(common + ["-c", src, "-o", obj])
+            jobs.append(common + EXTRA_FLAGS.get(s, [])
+                        + ["-c", src, "-o", obj])
     for s in TORCH_SOURCES:
         src = os.path.join(CSRC, s)
         obj = os.path.join(BUILD, s.replace(".cpp", ".o"))

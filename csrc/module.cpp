@@ -2172,6 +2172,74 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> gat_dots_backward(
     return {g_h, g_as, g_ad};
 }
 
+// Fused GATv2 attention (gatv2_kernels.hip): xl [n_src, heads*C] source
+// rows, xr one target row per dst segment (more rows allowed), att
+// [heads*C] fp32.  Returns (out [n_dst, heads*C], lse [n_dst, heads]).
+// The operand checks shared by the forward and the backward binding:
+struct Gatv2Operands {
+    torch::Tensor xr, att;
+    int chead;
+    Gatv2Operands(const SegmentCall& c, const torch::Tensor& xr_in,
+                  const torch::Tensor& att_in, int64_t heads)
+        : chead(c.chead(heads)) {
+        TORCH_CHECK(chead % 4 == 0 && c.dim <= 1024, c.op,
+                    ": needs per-head channels % 4 == 0 and heads * channels"
+                    " <= 1024, got ", heads, " x ", chead);
+        TORCH_CHECK(xr_in.dim() == 2 && xr_in.size(0) >= c.n_dst, c.op,
+                    ": xr needs a row per dst_ptr segment");
+        xr = c.arg("xr", xr_in, c.feat.scalar_type(),
+                   {xr_in.size(0), c.dim});
+        att = c.arg("att", att_in.reshape(-1), torch::kFloat32, {c.dim});
+    }
+};
+
+std::tuple<torch::Tensor, torch::Tensor> gatv2_attn(
+    torch::Tensor xl, torch::Tensor xr, torch::Tensor att, torch::Tensor src,
+    torch::Tensor dst_ptr, int64_t heads, double slope) {
+    SegmentCall c("gatv2_attn", "xl", xl, false, &src, &dst_ptr);
+    Gatv2Operands o(c, xr, att, heads);
+    auto out = torch::empty({c.n_dst, c.dim}, c.feat.options());
+    auto lse = torch::empty({c.n_dst, heads},
+                            c.feat.options().dtype(torch::kFloat32));
+    qk::launch_gatv2_attn_fwd(c.stream, c.elem, c.feat.data_ptr(),
+                              o.xr.data_ptr(), o.att.data_ptr<float>(),
+                              c.src_ptr(), c.dst_ptr_ptr(), c.n_dst,
+                              (int)heads, o.chead, (float)slope,
+                              out.data_ptr(), lse.data_ptr<float>());
+    return {out, lse};
+}
+
+// (g_xl [n_src, D], g_xr shaped like xr with zero rows past n_dst,
+// g_att [D] fp32); an output whose need_* flag is false is undefined.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> gatv2_attn_backward(
+    torch::Tensor grad_out, torch::Tensor xl, torch::Tensor xr,
+    torch::Tensor att, torch::Tensor out, torch::Tensor lse,
+    torch::Tensor src, torch::Tensor dst_ptr, int64_t heads, double slope,
+    bool need_gxl, bool need_gxr, bool need_gatt) {
+    SegmentCall c("gatv2_attn_backward", "xl", xl, false, &src, &dst_ptr);
+    Gatv2Operands o(c, xr, att, heads);
+    grad_out = c.arg("grad_out", grad_out, c.feat.scalar_type(),
+                     {c.n_dst, c.dim});
+    out = c.arg("out", out, c.feat.scalar_type(), {c.n_dst, c.dim});
+    lse = c.arg("lse", lse, torch::kFloat32, {c.n_dst, heads});
+    torch::Tensor g_xl, g_xr, g_att;
+    if (need_gxl) g_xl = torch::zeros_like(c.feat);
+    if (need_gxr) {
+        g_xr = torch::empty_like(o.xr);
+        g_xr.narrow(0, c.n_dst, o.xr.size(0) - c.n_dst).zero_();
+    }
+    if (need_gatt) g_att = torch::zeros_like(o.att);
+    qk::launch_gatv2_attn_bwd(
+        c.stream, c.elem, grad_out.data_ptr(), c.feat.data_ptr(),
+        o.xr.data_ptr(), o.att.data_ptr<float>(), out.data_ptr(),
+        lse.data_ptr<float>(), c.src_ptr(), c.dst_ptr_ptr(), c.n_dst,
+        (int)heads, o.chead, (float)slope,
+        need_gxl ? g_xl.data_ptr() : nullptr,
+        need_gxr ? g_xr.data_ptr() : nullptr,
+        need_gatt ? g_att.data_ptr<float>() : nullptr);
+    return {g_xl, g_xr, g_att};
+}
+
 void init_p2p(const std::vector<int>& devices) {
     // On an 8x MI355X node every pair is xGMI-connected: enable the full
     // clique (reference init_p2p, quiver_feature.cu:378-421; no NVLink-style
@@ -2428,6 +2496,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gat_alpha", &gat_alpha,
           "fused GAT attention coefficients over dst-sorted edges");
     m.def("gat_alpha_backward", &gat_alpha_backward);
+    m.def("gatv2_attn", &gatv2_attn,
+          "fused GATv2 attention over dst-sorted edges: (out, lse)");
+    m.def("gatv2_attn_backward", &gatv2_attn_backward);
     m.def("segment_softmax", &segment_softmax,
           "numerically-stable softmax over dst-sorted edge segments");
     m.def("segment_softmax_backward", &segment_softmax_backward);

@@ -15,6 +15,7 @@
 //   segment_kernels.hip  message passing over dst-sorted edges: segment
 //                        mean, weighted segment sum, segment softmax, GAT
 //                        attention coefficients and dots
+//   gatv2_kernels.hip    fused GATv2 attention over dst-sorted edges
 //
 // Capability parity map (reference: quiver-team/torch-quiver):
 //   sample_kernels.hip  ~ srcs/cpp/include/quiver/cuda_random.cu.hpp +
@@ -363,5 +364,29 @@ void launch_gat_dots_bwd(hipStream_t s, Elem et, const void* h,
                          const float* g_asrc, const float* g_adst,
                          int64_t n, int64_t n_dst, int heads, int chead,
                          void* g_h, float* g_att_src, float* g_att_dst);
+
+// ---------- fused GATv2 attention (gatv2_kernels.hip) ---------------------
+//
+// xl [n_src, H*C] and xr [>= n_dst, H*C] feature rows, att [H*C] fp32:
+//   logit[e,h] = <att[h,:], leaky_relu(xl[src[e],h,:] + xr[d,h,:])>
+//   out[d,h,:] = sum_e softmax_seg(logit)[e,h] * xl[src[e],h,:]
+//   lse[d,h]   = log sum_e exp(logit[e,h])        (fp32, -inf when empty)
+// in one pass over each segment (online softmax, no per-edge tensor).
+// Throws unless C % 4 == 0 and H*C <= 1024.
+void launch_gatv2_attn_fwd(hipStream_t s, Elem et, const void* xl,
+                           const void* xr, const float* att,
+                           const int64_t* src, const int64_t* dst_ptr,
+                           int64_t n_dst, int heads, int chead, float slope,
+                           void* out, float* lse);
+// Gradients of the above from the saved out and lse, one pass per segment.
+// A null g_xl / g_xr / g_att skips that output.  g_xl [n_src, H*C] and
+// g_att [H*C] are accumulated with atomics (pre-zeroed); g_xr rows
+// [0, n_dst) are written directly.
+void launch_gatv2_attn_bwd(hipStream_t s, Elem et, const void* grad_out,
+                           const void* xl, const void* xr, const float* att,
+                           const void* out, const float* lse,
+                           const int64_t* src, const int64_t* dst_ptr,
+                           int64_t n_dst, int heads, int chead, float slope,
+                           void* g_xl, void* g_xr, float* g_att);
 
 }  // namespace qk

@@ -14,9 +14,10 @@
 // The segment-mean kernels size their lane group to the row (the smallest
 // power of two of lanes covering dim/4 fp32 or dim/8 bf16 channels, at
 // most one wave) and keep up to 8 gathered rows in flight per group.
-#include <hip/hip_bf16.h>
-
-#include "qk_common.h"
+//
+// vec4io, atomio, lrelu, grid_for and launch_for live in segment_io.h,
+// shared with gatv2_kernels.hip.
+#include "segment_io.h"
 
 namespace qk {
 
@@ -26,39 +27,6 @@ constexpr int BLOCK = 256;
 constexpr int SUB = 16;                     // lanes per dst segment
 constexpr int ROWS_PER_BLOCK = BLOCK / SUB;
 constexpr int VPL = 4;                      // floats per lane per chunk
-
-// 4-element load/store in fp32 working precision for fp32 and bf16
-// element types (bf16 goes through 4-byte bf16x2 pairs: aligned for any
-// even dim; the value math stays fp32 and only stores round).
-template <typename T> struct vec4io;
-template <> struct vec4io<float> {
-    static __device__ __forceinline__ void load(const float* p, float v[4]) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    }
-    static __device__ __forceinline__ void store(float* p, const float v[4]) {
-        *reinterpret_cast<float4*>(p) = float4{v[0], v[1], v[2], v[3]};
-    }
-};
-template <> struct vec4io<__hip_bfloat16> {
-    static __device__ __forceinline__ void load(const __hip_bfloat16* p,
-                                                float v[4]) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const float2 f = __bfloat1622float2(
-                *reinterpret_cast<const __hip_bfloat162*>(p + 2 * i));
-            v[2 * i] = f.x;
-            v[2 * i + 1] = f.y;
-        }
-    }
-    static __device__ __forceinline__ void store(__hip_bfloat16* p,
-                                                 const float v[4]) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-            *reinterpret_cast<__hip_bfloat162*>(p + 2 * i) =
-                __float22bfloat162_rn(float2{v[2 * i], v[2 * i + 1]});
-    }
-};
 
 // ---- segment mean: lane group sized to the row ---------------------------
 // One group of LANES lanes per dst, LANES = smallest power of two with
@@ -229,29 +197,6 @@ segment_mean_fwd_kernel(const T* __restrict__ x,
 // segments for 100 floats or 256 bf16.  bf16 uses the packed-bf16 atomic
 // on channel pairs (gradient buffer lives in ordinary HBM, no
 // system-scope requirement).
-template <typename T> struct atomio;
-template <> struct atomio<float> {
-    using word_t = float;
-    static constexpr int EPW = 1;  // elements per word
-    static __device__ __forceinline__ word_t scale(word_t g, float inv) {
-        return g * inv;
-    }
-    static __device__ __forceinline__ void add(word_t* p, word_t v) {
-        atomicAdd(p, v);
-    }
-};
-template <> struct atomio<__hip_bfloat16> {
-    using word_t = __hip_bfloat162;
-    static constexpr int EPW = 2;
-    static __device__ __forceinline__ word_t scale(word_t g, float inv) {
-        const float2 f = __bfloat1622float2(g);
-        return __float22bfloat162_rn(float2{f.x * inv, f.y * inv});
-    }
-    static __device__ __forceinline__ void add(word_t* p, word_t v) {
-        unsafeAtomicAdd(p, v);
-    }
-};
-
 template <typename T, int LANES>
 __global__ void __launch_bounds__(BLOCK)
 segment_mean_bwd_kernel(const T* __restrict__ grad_out,
@@ -502,10 +447,6 @@ segment_softmax_bwd_kernel(const float* __restrict__ grad_out,
 // pre-activation is recomputed per pass (asrc/adst stay L2-hot) instead
 // of materializing any [E,H] intermediate.
 
-__device__ __forceinline__ float lrelu(float v, float slope) {
-    return v > 0.f ? v : v * slope;
-}
-
 __global__ void __launch_bounds__(BLOCK)
 gat_alpha_fwd_kernel(const float* __restrict__ asrc,
                      const float* __restrict__ adst,
@@ -677,24 +618,8 @@ gat_dots_bwd_kernel(const HT* __restrict__ h,
     }
 }
 
-inline int grid_for(int64_t work, int per_block) {
-    int64_t blocks = (work + per_block - 1) / per_block;
-    if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;
-    return (int)blocks;
-}
-
 // ---- launch layer ---------------------------------------------------------
-// Runs f with a tag whose ::type is the element type named by `et`, unless
-// there are no rows to work on, and reports a failed launch.  Every
-// launcher with dtype-dependent buffers goes through it.
-template <typename T> struct elem_tag { using type = T; };
-template <typename F> void launch_for(Elem et, int64_t rows, F&& f) {
-    if (rows == 0) return;
-    if (et == Elem::bf16) f(elem_tag<__hip_bfloat16>{});
-    else f(elem_tag<float>{});
-    QK_CHECK_HIP(hipGetLastError());
-}
+// (grid_for and launch_for: segment_io.h)
 
 // Layout assumptions of the kernels, checked once per launch.
 void check_rows(const char* op, Elem et, int64_t dim) {

@@ -6,8 +6,8 @@ bench.py live here.  The layers follow PyG's bipartite convention: forward
 ((x_src, x_dst), edge_index, size) with edge_index[0] indexing x_src and
 edge_index[1] indexing x_dst — exactly what GraphSageSampler's adjs feed.
 On GPU tensors with dst-sorted edges (the sampler's layout) aggregation and
-attention run on the fused HIP segment kernels (csrc/segment_kernels.hip)
-through the autograd functions below; other inputs take the plain torch
+attention run on the fused HIP segment kernels (csrc/segment_kernels.hip,
+csrc/gatv2_kernels.hip) through the autograd functions below; other inputs take the plain torch
 index_add / scatter_reduce chain.
 """
 from typing import Tuple
@@ -22,7 +22,8 @@ from . import _ext
 # not clone()/.to()/indexing)
 from .pyg.sage_sampler import DST_PTR_ATTR
 
-__all__ = ["SAGEConv", "GATConv", "GraphSAGE", "GAT", "QLinear"]
+__all__ = ["SAGEConv", "GATConv", "GATv2Conv", "GraphSAGE", "GAT",
+           "QLinear"]
 
 
 def _as_pair(x):
@@ -149,6 +150,31 @@ class _GatAlpha(torch.autograd.Function):
             grad_alpha, alpha, asrc, adst, src, dst_ptr, ctx.heads,
             ctx.slope)
         return g_asrc, g_adst, None, None, None, None, None
+
+
+class _GatV2Attn(torch.autograd.Function):
+    """Fused GATv2 attention over dst-sorted edges (csrc/gatv2_kernels.hip):
+    out[d,h,:] = sum_e softmax_seg(<att[h], leaky_relu(xl[src_e,h] +
+    xr[d,h])>) * xl[src_e,h,:], one pass over each segment in either
+    direction (online softmax forward, alpha recomputed from the saved
+    log-sum-exp backward) and no [E,H,C] tensor at all."""
+
+    @staticmethod
+    def forward(ctx, xl, xr, att, src, dst_ptr, heads, slope):
+        out, lse = _ext.gatv2_attn(xl, xr, att, src, dst_ptr, heads, slope)
+        ctx.save_for_backward(xl, xr, att, out, lse, src, dst_ptr)
+        ctx.heads, ctx.slope = heads, slope
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        xl, xr, att, out, lse, src, dst_ptr = ctx.saved_tensors
+        need = ctx.needs_input_grad[:3]
+        g_xl, g_xr, g_att = _ext.gatv2_attn_backward(
+            grad_out.contiguous(), xl, xr, att, out, lse, src, dst_ptr,
+            ctx.heads, ctx.slope, *need)
+        return (g_xl if need[0] else None, g_xr if need[1] else None,
+                g_att if need[2] else None, None, None, None, None)
 
 
 class _QLinearFn(torch.autograd.Function):
@@ -440,6 +466,106 @@ class GATConv(nn.Module):
         return out.to(out_dtype) if out.dtype != out_dtype else out
 
 
+# widest heads * out_channels the fused GATv2 kernels keep in registers
+_GATV2_MAX_DIM = 1024
+
+
+class GATv2Conv(nn.Module):
+    """GATv2 convolution (Brody et al., "How Attentive are Graph Attention
+    Networks?"), PyG's parameter names and semantics: lin_l projects the
+    source rows, lin_r the target rows (the same module when
+    share_weights), and the logit of an edge is
+    att[h] . leaky_relu(lin_l(x_src)[src] + lin_r(x_dst)[dst]).
+
+    With sorted_dst=True (GraphSageSampler's adjs) on GPU tensors of fp32
+    or bf16, out_channels % 4 == 0 and heads * out_channels <= 1024, the
+    attention and aggregation run in the fused kernels of
+    csrc/gatv2_kernels.hip.  Attention dropout in training mode, and any
+    other input, takes the plain torch chain below."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True,
+                 negative_slope=0.2, dropout=0.0, bias=True,
+                 share_weights=False, sorted_dst=False):
+        super().__init__()
+        self.sorted_dst = sorted_dst
+        self.heads = heads
+        self.out_channels = out_channels
+        self.concat = concat
+        self.negative_slope = negative_slope
+        self.dropout = dropout
+        self.share_weights = share_weights
+        self.lin_l = QLinear(in_channels, heads * out_channels, bias=bias)
+        self.lin_r = (self.lin_l if share_weights else
+                      QLinear(in_channels, heads * out_channels, bias=bias))
+        self.att = nn.Parameter(torch.empty(1, heads, out_channels))
+        out_dim = heads * out_channels if concat else out_channels
+        self.bias = nn.Parameter(torch.zeros(out_dim)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for lin in ((self.lin_l,) if self.share_weights
+                    else (self.lin_l, self.lin_r)):
+            nn.init.xavier_uniform_(lin.weight)
+            if lin.bias is not None:
+                nn.init.zeros_(lin.bias)
+        nn.init.xavier_uniform_(self.att)
+        if self.bias is not None:
+            nn.init.zeros_(self.bias)
+
+    def _fused_ok(self, xl, dst):
+        H, C = self.heads, self.out_channels
+        return (self.sorted_dst and xl.is_cuda and dst.numel() > 0
+                and xl.dtype in (torch.float32, torch.bfloat16)
+                and C % 4 == 0 and H * C <= _GATV2_MAX_DIM
+                and not (self.training and self.dropout > 0))
+
+    def forward(self, x, edge_index, size: Tuple[int, int] = None):
+        x_src, x_dst = _as_pair(x)
+        src, dst = edge_index[0], edge_index[1]
+        H, C = self.heads, self.out_channels
+        n_dst = x_dst.size(0) if size is None else int(size[1])
+
+        xl = self.lin_l(x_src)
+        if self.share_weights and _is_prefix(x_src, x_dst):
+            # bipartite prefix convention: the target rows are already
+            # projected, as the leading rows of xl
+            xr = xl[:x_dst.size(0)]
+        else:
+            xr = self.lin_r(x_dst)
+
+        if self._fused_ok(xl, dst):
+            out = _GatV2Attn.apply(
+                xl, xr, self.att.reshape(-1).float(), src,
+                _dst_ptr_for(edge_index, n_dst), H, self.negative_slope)
+            out = out if self.concat else out.view(n_dst, H, C).mean(1)
+        else:
+            xl3 = xl.view(-1, H, C)
+            z = F.leaky_relu(xl3[src] + xr.view(-1, H, C)[dst],
+                             self.negative_slope)        # [E, H, C]
+            alpha = (z * self.att).sum(-1)               # [E, H]
+            # segment softmax over the incoming edges of each dst
+            amax = torch.full((n_dst, H), float("-inf"), dtype=alpha.dtype,
+                              device=alpha.device)
+            amax = amax.scatter_reduce(
+                0, dst.unsqueeze(-1).expand_as(alpha), alpha, reduce="amax",
+                include_self=True)
+            alpha = (alpha - amax[dst]).exp()
+            denom = torch.zeros((n_dst, H), dtype=alpha.dtype,
+                                device=alpha.device)
+            denom.index_add_(0, dst, alpha)
+            alpha = alpha / denom[dst].clamp(min=1e-16)
+            if self.training and self.dropout > 0:
+                alpha = F.dropout(alpha, p=self.dropout)
+            out = torch.zeros((n_dst, H, C), dtype=xl.dtype,
+                              device=xl.device)
+            out.index_add_(0, dst, xl3[src] * alpha.unsqueeze(-1))
+            out = (out.reshape(n_dst, H * C) if self.concat
+                   else out.mean(1))
+        if self.bias is not None:
+            out = out + self.bias
+        return out
+
+
 class GraphSAGE(nn.Module):
     """Multi-layer GraphSAGE matching the reference examples' training/
     inference loop (forward(x, adjs) over per-hop bipartite graphs)."""
@@ -487,24 +613,26 @@ class GraphSAGE(nn.Module):
 
 class GAT(nn.Module):
     def __init__(self, in_channels, hidden_channels, out_channels,
-                 num_layers=2, heads=4, dropout=0.5, sorted_dst=True):
+                 num_layers=2, heads=4, dropout=0.5, sorted_dst=True,
+                 v2=False):
         super().__init__()
         self.num_layers = num_layers
         self.dropout = dropout
         self.convs = nn.ModuleList()
+        conv = GATv2Conv if v2 else GATConv
         # sorted_dst: GraphSageSampler emits dst-sorted adjs -> fused kernel
         if num_layers == 1:
-            self.convs.append(GATConv(in_channels, out_channels, heads=1,
-                                      sorted_dst=sorted_dst))
+            self.convs.append(conv(in_channels, out_channels, heads=1,
+                                   sorted_dst=sorted_dst))
         else:
-            self.convs.append(GATConv(in_channels, hidden_channels,
-                                      heads=heads, sorted_dst=sorted_dst))
+            self.convs.append(conv(in_channels, hidden_channels,
+                                   heads=heads, sorted_dst=sorted_dst))
             for _ in range(num_layers - 2):
-                self.convs.append(GATConv(hidden_channels * heads,
-                                          hidden_channels, heads=heads,
-                                          sorted_dst=sorted_dst))
-            self.convs.append(GATConv(hidden_channels * heads, out_channels,
-                                      heads=1, sorted_dst=sorted_dst))
+                self.convs.append(conv(hidden_channels * heads,
+                                       hidden_channels, heads=heads,
+                                       sorted_dst=sorted_dst))
+            self.convs.append(conv(hidden_channels * heads, out_channels,
+                                   heads=1, sorted_dst=sorted_dst))
 
     def forward(self, x, adjs):
         for i, (edge_index, _, size) in enumerate(adjs):
