@@ -14,7 +14,10 @@ alternating fused and chain, median reported.  Peak memory is the
 allocator's peak over one fwd+bwd minus what was allocated before it.
 Both paths get the same parameters and inputs; their outputs are compared.
 
-  python benchmarks/bench_gatv2.py [--md FILE]
+--edge-dim D gives both layers edge_dim=D and a random [E, D] edge_attr in
+the row dtype (one row per edge); --shapes picks rows of SHAPES by index.
+
+  python benchmarks/bench_gatv2.py [--md FILE] [--edge-dim D] [--shapes I..]
 """
 import argparse
 import json
@@ -43,11 +46,11 @@ def make_inputs(n_dst, fanout, n_src, dtype):
     return x.requires_grad_(), ei
 
 
-def make_step(conv, x, ei, n_dst, backward):
+def make_step(conv, x, ei, n_dst, backward, edge_attr=None):
     size = (x.size(0), n_dst)
 
     def step():
-        out = conv((x, x[:n_dst]), ei, size)
+        out = conv((x, x[:n_dst]), ei, size, edge_attr=edge_attr)
         if backward:
             x.grad = None
             conv.zero_grad(set_to_none=True)
@@ -78,27 +81,41 @@ def peak_mib(step):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--md", help="also write the table to this file")
+    ap.add_argument("--edge-dim", type=int, default=None,
+                    help="edge feature width (default: no edge features)")
+    ap.add_argument("--shapes", type=int, nargs="+",
+                    default=list(range(len(SHAPES))),
+                    help="indices into SHAPES (default: all)")
     args = ap.parse_args()
+    kw = {} if args.edge_dim is None else dict(edge_dim=args.edge_dim)
     assert torch.cuda.is_available(), "bench_gatv2 needs a GPU"
     lines = ["| dtype | n_dst | fanout | n_src | mode | fused ms | chain ms |"
              " speedup | fused peak MiB | chain peak MiB |",
              "|---|---|---|---|---|---|---|---|---|---|"]
     for dtype in (torch.float32, torch.bfloat16):
-        for n_dst, fanout, n_src in SHAPES:
+        for n_dst, fanout, n_src in (SHAPES[i] for i in args.shapes):
             x, ei = make_inputs(n_dst, fanout, n_src, dtype)
+            ea = None
+            if args.edge_dim is not None:
+                ea = torch.randn(ei.size(1), args.edge_dim,
+                                 generator=torch.Generator().manual_seed(1)
+                                 ).to("cuda", dtype)
             torch.manual_seed(0)
-            convs = {"fused": GATv2Conv(IN, C, heads=H, sorted_dst=True),
-                     "chain": GATv2Conv(IN, C, heads=H, sorted_dst=False)}
+            convs = {"fused": GATv2Conv(IN, C, heads=H, sorted_dst=True,
+                                        **kw),
+                     "chain": GATv2Conv(IN, C, heads=H, sorted_dst=False,
+                                        **kw)}
             convs["chain"].load_state_dict(convs["fused"].state_dict())
             for c in convs.values():
                 c.to("cuda", dtype)
             with torch.no_grad():
-                a, b = (convs[k]((x, x[:n_dst]), ei, (n_src, n_dst)).float()
+                a, b = (convs[k]((x, x[:n_dst]), ei, (n_src, n_dst),
+                                 edge_attr=ea).float()
                         for k in ("fused", "chain"))
                 diff = ((a - b).abs().max() / b.abs().max()).item()
             del a, b
             for backward in (False, True):
-                steps = {k: make_step(c, x, ei, n_dst, backward)
+                steps = {k: make_step(c, x, ei, n_dst, backward, ea)
                          for k, c in convs.items()}
                 iters = {}
                 for k, s in steps.items():
@@ -126,7 +143,7 @@ def main():
                     f"{rec['mode']} | {med['fused']:.3f} | {med['chain']:.3f}"
                     f" | {med['chain'] / med['fused']:.2f}x | "
                     f"{peak['fused']:.0f} | {peak['chain']:.0f} |")
-            del x, ei, convs, steps
+            del x, ei, ea, convs, steps
             torch.cuda.empty_cache()
     table = "\n".join(lines)
     print(table)

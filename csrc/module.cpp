@@ -2240,6 +2240,100 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> gatv2_attn_backward(
     return {g_xl, g_xr, g_att};
 }
 
+// Edge-feature operands of gatv2_attn_edge and its backward: edge_attr
+// [R, D] in the row dtype, edge_id (optional) int64 [E] naming the row of
+// each edge (else row e for edge e), w_edge [D, heads*C] fp32.  edge_id
+// values are not range-checked (that would cost a sync).
+struct Gatv2EdgeOperands {
+    torch::Tensor attr, id, w;
+    int dim;
+    Gatv2EdgeOperands(const SegmentCall& c,
+                      const torch::Tensor& attr_in,
+                      const c10::optional<torch::Tensor>& id_in,
+                      const torch::Tensor& w_in) {
+        TORCH_CHECK(attr_in.dim() == 2 && attr_in.is_contiguous() &&
+                    attr_in.size(1) >= 1, c.op,
+                    ": edge_attr must be 2-D and contiguous with at least "
+                    "one column, got ", attr_in.sizes());
+        attr = c.arg("edge_attr", attr_in, c.feat.scalar_type(),
+                     attr_in.sizes());
+        const int64_t n_edges = c.src.numel();
+        if (id_in.has_value())
+            id = c.arg("edge_id", *id_in, torch::kInt64, {n_edges});
+        else
+            TORCH_CHECK(attr.size(0) >= n_edges, c.op, ": edge_attr has ",
+                        attr.size(0), " rows for ", n_edges, " edges");
+        w = c.arg("w_edge", w_in, torch::kFloat32, {attr.size(1), c.dim});
+        TORCH_CHECK(attr.size(1) * c.dim <= 8192, c.op,
+                    ": needs edge_dim * heads * channels <= 8192, got ",
+                    attr.size(1), " * ", c.dim);
+        dim = (int)attr.size(1);
+    }
+    const int64_t* id_ptr() const {
+        return id.defined() ? id.data_ptr<int64_t>() : nullptr;
+    }
+};
+
+// gatv2_attn with edge features (see Gatv2EdgeOperands)
+std::tuple<torch::Tensor, torch::Tensor> gatv2_attn_edge(
+    torch::Tensor xl, torch::Tensor xr, torch::Tensor att,
+    torch::Tensor edge_attr, c10::optional<torch::Tensor> edge_id,
+    torch::Tensor w_edge, torch::Tensor src, torch::Tensor dst_ptr,
+    int64_t heads, double slope) {
+    SegmentCall c("gatv2_attn_edge", "xl", xl, false, &src, &dst_ptr);
+    Gatv2Operands o(c, xr, att, heads);
+    Gatv2EdgeOperands e(c, edge_attr, edge_id, w_edge);
+    auto out = torch::empty({c.n_dst, c.dim}, c.feat.options());
+    auto lse = torch::empty({c.n_dst, heads},
+                            c.feat.options().dtype(torch::kFloat32));
+    qk::launch_gatv2_attn_edge_fwd(
+        c.stream, c.elem, c.feat.data_ptr(), o.xr.data_ptr(),
+        o.att.data_ptr<float>(), e.attr.data_ptr(), e.id_ptr(),
+        e.w.data_ptr<float>(), e.dim, c.src_ptr(), c.dst_ptr_ptr(), c.n_dst,
+        (int)heads, o.chead, (float)slope, out.data_ptr(),
+        lse.data_ptr<float>());
+    return {out, lse};
+}
+
+// gatv2_attn_backward with edge features: (g_xl, g_xr, g_att, g_w
+// [D, heads*C] fp32); there is no gradient for edge_attr.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
+gatv2_attn_edge_backward(
+    torch::Tensor grad_out, torch::Tensor xl, torch::Tensor xr,
+    torch::Tensor att, torch::Tensor edge_attr,
+    c10::optional<torch::Tensor> edge_id, torch::Tensor w_edge,
+    torch::Tensor out, torch::Tensor lse, torch::Tensor src,
+    torch::Tensor dst_ptr, int64_t heads, double slope, bool need_gxl,
+    bool need_gxr, bool need_gatt, bool need_gw) {
+    SegmentCall c("gatv2_attn_edge_backward", "xl", xl, false, &src,
+                  &dst_ptr);
+    Gatv2Operands o(c, xr, att, heads);
+    Gatv2EdgeOperands e(c, edge_attr, edge_id, w_edge);
+    grad_out = c.arg("grad_out", grad_out, c.feat.scalar_type(),
+                     {c.n_dst, c.dim});
+    out = c.arg("out", out, c.feat.scalar_type(), {c.n_dst, c.dim});
+    lse = c.arg("lse", lse, torch::kFloat32, {c.n_dst, heads});
+    torch::Tensor g_xl, g_xr, g_att, g_w;
+    if (need_gxl) g_xl = torch::zeros_like(c.feat);
+    if (need_gxr) {
+        g_xr = torch::empty_like(o.xr);
+        g_xr.narrow(0, c.n_dst, o.xr.size(0) - c.n_dst).zero_();
+    }
+    if (need_gatt) g_att = torch::zeros_like(o.att);
+    if (need_gw) g_w = torch::zeros_like(e.w);
+    qk::launch_gatv2_attn_edge_bwd(
+        c.stream, c.elem, grad_out.data_ptr(), c.feat.data_ptr(),
+        o.xr.data_ptr(), o.att.data_ptr<float>(), e.attr.data_ptr(),
+        e.id_ptr(), e.w.data_ptr<float>(), e.dim, out.data_ptr(),
+        lse.data_ptr<float>(), c.src_ptr(), c.dst_ptr_ptr(), c.n_dst,
+        (int)heads, o.chead, (float)slope,
+        need_gxl ? g_xl.data_ptr() : nullptr,
+        need_gxr ? g_xr.data_ptr() : nullptr,
+        need_gatt ? g_att.data_ptr<float>() : nullptr,
+        need_gw ? g_w.data_ptr<float>() : nullptr);
+    return {g_xl, g_xr, g_att, g_w};
+}
+
 void init_p2p(const std::vector<int>& devices) {
     // On an 8x MI355X node every pair is xGMI-connected: enable the full
     // clique (reference init_p2p, quiver_feature.cu:378-421; no NVLink-style
@@ -2499,6 +2593,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gatv2_attn", &gatv2_attn,
           "fused GATv2 attention over dst-sorted edges: (out, lse)");
     m.def("gatv2_attn_backward", &gatv2_attn_backward);
+    m.def("gatv2_attn_edge", &gatv2_attn_edge,
+          "gatv2_attn with edge features projected inside the kernel");
+    m.def("gatv2_attn_edge_backward", &gatv2_attn_edge_backward);
     m.def("segment_softmax", &segment_softmax,
           "numerically-stable softmax over dst-sorted edge segments");
     m.def("segment_softmax_backward", &segment_softmax_backward);

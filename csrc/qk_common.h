@@ -389,4 +389,35 @@ void launch_gatv2_attn_bwd(hipStream_t s, Elem et, const void* grad_out,
                            int64_t n_dst, int heads, int chead, float slope,
                            void* g_xl, void* g_xr, float* g_att);
 
+// The same with edge features inside the non-linearity:
+//   logit[e,h] = <att[h,:], leaky_relu(xl[src[e],h,:] + xr[d,h,:] +
+//                                      (edge_attr[row(e)] @ w_edge)[h,:])>
+// edge_attr [R, edge_dim] rows of the element type, w_edge [edge_dim, H*C]
+// fp32, row(e) = edge_id[e] when edge_id is given, else e (the position in
+// the dst-sorted edge list).  The projection is done in the kernels: no
+// per-edge tensor is written.  Row ids are not range-checked.  Throws
+// unless also 1 <= edge_dim and edge_dim * H*C <= 8192 (w_edge and the
+// backward's g_w accumulator share one block's LDS), and H times the
+// 4-byte words of a head rounded up to a power of two is at most 1024.
+void launch_gatv2_attn_edge_fwd(hipStream_t s, Elem et, const void* xl,
+                                const void* xr, const float* att,
+                                const void* edge_attr, const int64_t* edge_id,
+                                const float* w_edge, int edge_dim,
+                                const int64_t* src, const int64_t* dst_ptr,
+                                int64_t n_dst, int heads, int chead,
+                                float slope, void* out, float* lse);
+// g_w [edge_dim, H*C] fp32 += sum_e edge_attr[row(e)]^T (g_e * att *
+// lrelu'(z[e])), accumulated with atomics (pre-zeroed), null to skip it;
+// the other outputs as in launch_gatv2_attn_bwd.  No gradient for
+// edge_attr.
+void launch_gatv2_attn_edge_bwd(hipStream_t s, Elem et, const void* grad_out,
+                                const void* xl, const void* xr,
+                                const float* att, const void* edge_attr,
+                                const int64_t* edge_id, const float* w_edge,
+                                int edge_dim, const void* out,
+                                const float* lse, const int64_t* src,
+                                const int64_t* dst_ptr, int64_t n_dst,
+                                int heads, int chead, float slope, void* g_xl,
+                                void* g_xr, float* g_att, float* g_w);
+
 }  // namespace qk

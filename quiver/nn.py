@@ -10,6 +10,7 @@ attention run on the fused HIP segment kernels (csrc/segment_kernels.hip,
 csrc/gatv2_kernels.hip) through the autograd functions below; other inputs take the plain torch
 index_add / scatter_reduce chain.
 """
+import functools
 from typing import Tuple
 
 import torch
@@ -175,6 +176,40 @@ class _GatV2Attn(torch.autograd.Function):
             ctx.heads, ctx.slope, *need)
         return (g_xl if need[0] else None, g_xr if need[1] else None,
                 g_att if need[2] else None, None, None, None, None)
+
+
+class _GatV2AttnEdge(torch.autograd.Function):
+    """_GatV2Attn with edge features inside the non-linearity:
+    z = xl[src_e] + xr[d] + edge_attr[row_e] @ w_edge, row_e = edge_id[e]
+    when edge_id is given, else e.  The kernels project the D raw values of
+    an edge themselves, so no [E, H*C] tensor exists in either direction.
+    w_edge is lin_edge.weight ([H*C, D]); its gradient comes back in its
+    dtype.  edge_attr gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, xl, xr, att, edge_attr, edge_id, w_edge, src, dst_ptr,
+                heads, slope):
+        w = w_edge.detach().t().contiguous().float()       # [D, H*C]
+        out, lse = _ext.gatv2_attn_edge(xl, xr, att, edge_attr, edge_id, w,
+                                        src, dst_ptr, heads, slope)
+        ctx.save_for_backward(xl, xr, att, edge_attr, edge_id, w, out, lse,
+                              src, dst_ptr)
+        ctx.heads, ctx.slope, ctx.w_dtype = heads, slope, w_edge.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (xl, xr, att, edge_attr, edge_id, w, out, lse, src,
+         dst_ptr) = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        g_xl, g_xr, g_att, g_w = _ext.gatv2_attn_edge_backward(
+            grad_out.contiguous(), xl, xr, att, edge_attr, edge_id, w, out,
+            lse, src, dst_ptr, ctx.heads, ctx.slope, need[0], need[1],
+            need[2], need[5])
+        return (g_xl if need[0] else None, g_xr if need[1] else None,
+                g_att if need[2] else None, None, None,
+                g_w.t().to(ctx.w_dtype) if need[5] else None,
+                None, None, None, None)
 
 
 class _QLinearFn(torch.autograd.Function):
@@ -468,6 +503,18 @@ class GATConv(nn.Module):
 
 # widest heads * out_channels the fused GATv2 kernels keep in registers
 _GATV2_MAX_DIM = 1024
+# largest edge_dim * heads * out_channels of the fused edge-feature kernels:
+# the fp32 lin_edge weight and its gradient accumulator share one block's
+# LDS (2 * 4 * 8192 bytes = 64 KiB)
+_GATV2_MAX_EDGE_WEIGHT = 8192
+# When lin_edge's weight gradient is needed, the fused edge backward is bound
+# by its fp32 LDS atomics (edge_dim * heads * out_channels per two edges) and
+# was measured against the torch chain (profiles/SEGMENT_GATV2.md): faster
+# up to this weight size for bf16 rows and, for fp32 rows, only at the
+# smallest measured edge count; slower or level elsewhere, which goes to the
+# chain.
+_GATV2_EDGE_TRAIN_MAX_WEIGHT = 4096
+_GATV2_EDGE_TRAIN_FP32_MAX_EDGES = 16384
 
 
 class GATv2Conv(nn.Module):
@@ -481,13 +528,24 @@ class GATv2Conv(nn.Module):
     or bf16, out_channels % 4 == 0 and heads * out_channels <= 1024, the
     attention and aggregation run in the fused kernels of
     csrc/gatv2_kernels.hip.  Attention dropout in training mode, and any
-    other input, takes the plain torch chain below."""
+    other input, takes the plain torch chain below.
+
+    edge_dim=D adds lin_edge (no bias) and forward(..., edge_attr=,
+    edge_id=): lin_edge(edge_attr) joins the sum inside the leaky_relu; the
+    messages carry no edge term.  edge_attr is [E, D] with a row per column
+    of edge_index, or with edge_id (int64 [E], e.g. Adj.e_id of a sampler
+    built with return_eid=True) any table whose row edge_id[e] belongs to
+    edge e.  The fused kernels project the raw rows themselves when also
+    D * heads * out_channels <= 8192 and edge_attr needs no gradient; with
+    a weight gradient for lin_edge to compute, only where that was measured
+    faster than the torch chain (see _GATV2_EDGE_TRAIN_MAX_WEIGHT)."""
 
     def __init__(self, in_channels, out_channels, heads=1, concat=True,
                  negative_slope=0.2, dropout=0.0, bias=True,
-                 share_weights=False, sorted_dst=False):
+                 share_weights=False, sorted_dst=False, edge_dim=None):
         super().__init__()
         self.sorted_dst = sorted_dst
+        self.edge_dim = edge_dim
         self.heads = heads
         self.out_channels = out_channels
         self.concat = concat
@@ -497,6 +555,8 @@ class GATv2Conv(nn.Module):
         self.lin_l = QLinear(in_channels, heads * out_channels, bias=bias)
         self.lin_r = (self.lin_l if share_weights else
                       QLinear(in_channels, heads * out_channels, bias=bias))
+        self.lin_edge = (None if edge_dim is None else
+                         QLinear(edge_dim, heads * out_channels, bias=False))
         self.att = nn.Parameter(torch.empty(1, heads, out_channels))
         out_dim = heads * out_channels if concat else out_channels
         self.bias = nn.Parameter(torch.zeros(out_dim)) if bias else None
@@ -508,6 +568,8 @@ class GATv2Conv(nn.Module):
             nn.init.xavier_uniform_(lin.weight)
             if lin.bias is not None:
                 nn.init.zeros_(lin.bias)
+        if self.lin_edge is not None:
+            nn.init.xavier_uniform_(self.lin_edge.weight)
         nn.init.xavier_uniform_(self.att)
         if self.bias is not None:
             nn.init.zeros_(self.bias)
@@ -519,11 +581,54 @@ class GATv2Conv(nn.Module):
                 and C % 4 == 0 and H * C <= _GATV2_MAX_DIM
                 and not (self.training and self.dropout > 0))
 
-    def forward(self, x, edge_index, size: Tuple[int, int] = None):
+    def _checked_edge_attr(self, edge_attr, edge_id, n_edges):
+        if edge_attr is None:
+            if edge_id is not None:
+                raise ValueError("GATv2Conv: edge_id given without edge_attr")
+            return None
+        if self.edge_dim is None:
+            raise ValueError("GATv2Conv: edge_attr given to a layer built "
+                             "without edge_dim")
+        if edge_attr.dim() == 1:
+            edge_attr = edge_attr.view(-1, 1)
+        if edge_attr.dim() != 2 or edge_attr.size(1) != self.edge_dim:
+            raise ValueError(f"GATv2Conv: edge_attr must be [*, "
+                             f"{self.edge_dim}], got "
+                             f"{tuple(edge_attr.shape)}")
+        if edge_id is None and edge_attr.size(0) != n_edges:
+            raise ValueError(f"GATv2Conv: edge_attr has {edge_attr.size(0)} "
+                             f"rows for {n_edges} edges; pass edge_id to "
+                             "select rows of a table")
+        if edge_id is not None and edge_id.numel() != n_edges:
+            raise ValueError(f"GATv2Conv: edge_id has {edge_id.numel()} "
+                             f"entries for {n_edges} edges")
+        return edge_attr
+
+    def _fused_edge_ok(self, xl, edge_attr, edge_id, n_edges):
+        weight = self.edge_dim * self.heads * self.out_channels
+        if torch.is_grad_enabled() and self.lin_edge.weight.requires_grad \
+                and not (weight <= _GATV2_EDGE_TRAIN_MAX_WEIGHT
+                         and (xl.dtype == torch.bfloat16 or n_edges
+                              <= _GATV2_EDGE_TRAIN_FP32_MAX_EDGES)):
+            return False
+        # the kernels pad a head to a power of two of 4-byte words and the
+        # edge variant holds at most 1024 such slots
+        words = self.out_channels * xl.element_size() // 4
+        slots = self.heads * (1 << (words - 1).bit_length())
+        return (slots <= 1024
+                and edge_attr.is_cuda and not edge_attr.requires_grad
+                and edge_attr.is_floating_point()
+                and (edge_id is None or (edge_id.is_cuda
+                                         and edge_id.dtype == torch.int64))
+                and weight <= _GATV2_MAX_EDGE_WEIGHT)
+
+    def forward(self, x, edge_index, size: Tuple[int, int] = None,
+                edge_attr=None, edge_id=None):
         x_src, x_dst = _as_pair(x)
         src, dst = edge_index[0], edge_index[1]
         H, C = self.heads, self.out_channels
         n_dst = x_dst.size(0) if size is None else int(size[1])
+        edge_attr = self._checked_edge_attr(edge_attr, edge_id, src.numel())
 
         xl = self.lin_l(x_src)
         if self.share_weights and _is_prefix(x_src, x_dst):
@@ -533,15 +638,30 @@ class GATv2Conv(nn.Module):
         else:
             xr = self.lin_r(x_dst)
 
-        if self._fused_ok(xl, dst):
+        fused = self._fused_ok(xl, dst)
+        if fused and edge_attr is not None:
+            fused = self._fused_edge_ok(xl, edge_attr, edge_id, src.numel())
+        if fused and edge_attr is not None:
+            # the table stays as it is (edge_id selects rows in the kernel);
+            # a table of another float dtype is narrow: cast it whole
+            out = _GatV2AttnEdge.apply(
+                xl, xr, self.att.reshape(-1).float(),
+                edge_attr.to(xl.dtype).contiguous(), edge_id,
+                self.lin_edge.weight, src, _dst_ptr_for(edge_index, n_dst),
+                H, self.negative_slope)
+            out = out if self.concat else out.view(n_dst, H, C).mean(1)
+        elif fused:
             out = _GatV2Attn.apply(
                 xl, xr, self.att.reshape(-1).float(), src,
                 _dst_ptr_for(edge_index, n_dst), H, self.negative_slope)
             out = out if self.concat else out.view(n_dst, H, C).mean(1)
         else:
             xl3 = xl.view(-1, H, C)
-            z = F.leaky_relu(xl3[src] + xr.view(-1, H, C)[dst],
-                             self.negative_slope)        # [E, H, C]
+            z = xl3[src] + xr.view(-1, H, C)[dst]
+            if edge_attr is not None:
+                ea = edge_attr if edge_id is None else edge_attr[edge_id]
+                z = z + self.lin_edge(ea.to(xl.dtype)).view(-1, H, C)
+            z = F.leaky_relu(z, self.negative_slope)     # [E, H, C]
             alpha = (z * self.att).sum(-1)               # [E, H]
             # segment softmax over the incoming edges of each dst
             amax = torch.full((n_dst, H), float("-inf"), dtype=alpha.dtype,
@@ -614,12 +734,17 @@ class GraphSAGE(nn.Module):
 class GAT(nn.Module):
     def __init__(self, in_channels, hidden_channels, out_channels,
                  num_layers=2, heads=4, dropout=0.5, sorted_dst=True,
-                 v2=False):
+                 v2=False, edge_dim=None):
         super().__init__()
+        if edge_dim is not None and not v2:
+            raise ValueError("GAT: edge_dim needs v2=True (GATConv takes no "
+                             "edge features)")
         self.num_layers = num_layers
         self.dropout = dropout
         self.convs = nn.ModuleList()
         conv = GATv2Conv if v2 else GATConv
+        if edge_dim is not None:
+            conv = functools.partial(GATv2Conv, edge_dim=edge_dim)
         # sorted_dst: GraphSageSampler emits dst-sorted adjs -> fused kernel
         if num_layers == 1:
             self.convs.append(conv(in_channels, out_channels, heads=1,
@@ -634,10 +759,21 @@ class GAT(nn.Module):
             self.convs.append(conv(hidden_channels * heads, out_channels,
                                    heads=1, sorted_dst=sorted_dst))
 
-    def forward(self, x, adjs):
-        for i, (edge_index, _, size) in enumerate(adjs):
+    def forward(self, x, adjs, edge_attr=None):
+        """edge_attr: the graph's edge-feature table; each layer reads the
+        rows named by its hop's Adj.e_id, so the sampler must be built with
+        return_eid=True."""
+        for i, (edge_index, e_id, size) in enumerate(adjs):
             x_target = x[:size[1]]
-            x = self.convs[i]((x, x_target), edge_index, size)
+            if edge_attr is None:
+                x = self.convs[i]((x, x_target), edge_index, size)
+            else:
+                if e_id.numel() == 0 and edge_index.size(1) > 0:
+                    raise ValueError(
+                        "GAT: edge_attr given but Adj.e_id is empty; build "
+                        "the sampler with return_eid=True")
+                x = self.convs[i]((x, x_target), edge_index, size,
+                                  edge_attr=edge_attr, edge_id=e_id)
             if i != self.num_layers - 1:
                 x = F.elu(x, inplace=True)
                 if self.dropout > 0:
