@@ -168,20 +168,25 @@ void parallel_chunks(int64_t nchunk, int /*nthreads*/, F&& fn) {
     WorkerPool::inst().run(nchunk, [&fn](int64_t c) { fn(c, c + 1); });
 }
 
+// Exclusive scan of an int64 device tensor into a fresh prefix tensor; the
+// sum lands in *d_total on the device.  No host synchronisation.
+torch::Tensor exclusive_scan(const torch::Tensor& vals, int64_t* d_total,
+                             hipStream_t stream) {
+    int64_t n = vals.numel();
+    auto prefix = torch::empty_like(vals);
+    auto temp = torch::empty({(int64_t)qk::scan_temp_bytes(n)},
+                             vals.options().dtype(torch::kUInt8));
+    qk::launch_exclusive_scan(stream, temp.data_ptr(), temp.numel(),
+                              vals.data_ptr<int64_t>(),
+                              prefix.data_ptr<int64_t>(), n, d_total);
+    return prefix;
+}
+
 // Exclusive scan of an int64 device tensor; returns (prefix, total-on-host).
 std::pair<torch::Tensor, int64_t> exclusive_scan_total(
     const torch::Tensor& vals, hipStream_t stream) {
-    int64_t n = vals.numel();
-    auto prefix = torch::empty_like(vals);
-    auto temp = torch::empty(
-        {(int64_t)qk::scan_temp_bytes(n)},
-        torch::TensorOptions().dtype(torch::kUInt8).device(vals.device()));
-    auto d_total = torch::empty(
-        {1}, torch::TensorOptions().dtype(torch::kInt64).device(vals.device()));
-    qk::launch_exclusive_scan(stream, temp.data_ptr(), temp.numel(),
-                              vals.data_ptr<int64_t>(),
-                              prefix.data_ptr<int64_t>(), n,
-                              d_total.data_ptr<int64_t>());
+    auto d_total = torch::empty({1}, vals.options());
+    auto prefix = exclusive_scan(vals, d_total.data_ptr<int64_t>(), stream);
     int64_t h_total = 0;
     QK_CHECK_HIP(hipMemcpyAsync(&h_total, d_total.data_ptr(), sizeof(int64_t),
                                 hipMemcpyDeviceToHost, stream));
@@ -198,35 +203,18 @@ class GpuSampler {
                int device, bool dma_mode)
         : device_(device), dma_(dma_mode) {
         TORCH_CHECK(indptr.dtype() == torch::kInt64, "indptr must be int64");
-        TORCH_CHECK(indices.dtype() == torch::kInt64, "indices must be int64");
         DeviceScope g(device_);
-        auto dev = torch::Device(torch::kCUDA, device_);
         // indptr is always device-resident: it is read twice per seed and is
         // small (node_count+1).
-        indptr_ = indptr.contiguous().to(dev);
+        indptr_ = indptr.contiguous().to(torch::Device(torch::kCUDA, device_));
         node_count_ = indptr_.numel() - 1;
-        has_eid_ = eid.defined() && eid.numel() == indices.numel();
-        if (dma_) {
-            indices_ = indices.contiguous().to(dev);
-            indices_dptr_ = indices_.data_ptr<int64_t>();
-            if (has_eid_) {
-                eid_ = eid.contiguous().to(dev);
-                eid_dptr_ = eid_.data_ptr<int64_t>();
-            }
-        } else {
-            // ZERO_COPY: pin the host CSR columns and read them from kernels
-            // over PCIe (UVA).  Keeps graphs larger than HBM samplable.
-            TORCH_CHECK(indices.device().is_cpu(),
-                        "UVA mode expects CPU indices");
-            indices_ = pin_host(indices.contiguous());
-            indices_dptr_ = (int64_t*)host_devptr(indices_);
-            if (has_eid_) {
-                TORCH_CHECK(eid.device().is_cpu(),
-                            "UVA mode expects CPU edge ids");
-                eid_ = pin_host(eid.contiguous());
-                eid_dptr_ = (int64_t*)host_devptr(eid_);
-            }
-        }
+        const int64_t slots = indices.numel();
+        std::tie(indices_, indices_dptr_) =
+            place_column<int64_t>(indices, "indices", slots);
+        // an id map of another length means "no id map": ids are CSR slots
+        if (eid.defined() && eid.numel() == slots)
+            std::tie(eid_, eid_dptr_) =
+                place_column<int64_t>(eid, "edge ids", slots);
     }
 
     void set_seed(uint64_t seed) {
@@ -245,66 +233,20 @@ class GpuSampler {
         weight_ = torch::Tensor();
         weight_dptr_ = nullptr;
         if (!weight.defined() || weight.numel() == 0) return;
-        TORCH_CHECK(weight.dtype() == torch::kFloat32,
-                    "edge weights must be float32");
-        TORCH_CHECK(weight.numel() == indices_.numel(),
-                    "edge weights: one per CSR slot expected");
-        if (dma_) {
-            weight_ = weight.contiguous().to(
-                torch::Device(torch::kCUDA, device_));
-            weight_dptr_ = weight_.data_ptr<float>();
-        } else {
-            TORCH_CHECK(weight.device().is_cpu(),
-                        "UVA mode expects CPU edge weights");
-            weight_ = pin_host(weight.contiguous());
-            weight_dptr_ = (float*)host_devptr(weight_);
-        }
+        std::tie(weight_, weight_dptr_) =
+            place_column<float>(weight, "edge weights", indices_.numel());
     }
 
     std::tuple<torch::Tensor, torch::Tensor> sample_neighbor(
         int /*stream_id*/, torch::Tensor seeds, int k) {
-        DeviceScope g(device_);
-        auto stream = current_stream();
-        seeds = seeds.contiguous();
-        TORCH_CHECK(seeds.device().is_cuda(), "seeds must be on GPU");
-        int64_t n = seeds.numel();
-        auto opts =
-            torch::TensorOptions().dtype(torch::kInt64).device(seeds.device());
-        auto counts = torch::empty({n}, opts);
-        qk::launch_capped_degree(stream, indptr_.data_ptr<int64_t>(),
-                                 seeds.data_ptr<int64_t>(), n, k,
-                                 counts.data_ptr<int64_t>());
-        auto [prefix, total] = exclusive_scan_total(counts, stream);
-        auto out = torch::empty({total}, opts);
-        qk::launch_rng_bump(stream, rng_dev(stream));
-        draw(stream, seeds.data_ptr<int64_t>(), n, k,
-             prefix.data_ptr<int64_t>(), out.data_ptr<int64_t>(), nullptr, 0,
-             nullptr);
+        auto [out, counts, ids] = sample_impl(seeds, k, false);
         return {out, counts};
     }
 
     // sample_neighbor plus the id of every drawn edge, aligned with `out`.
     std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>
     sample_neighbor_eid(int /*stream_id*/, torch::Tensor seeds, int k) {
-        DeviceScope g(device_);
-        auto stream = current_stream();
-        seeds = seeds.contiguous();
-        TORCH_CHECK(seeds.device().is_cuda(), "seeds must be on GPU");
-        int64_t n = seeds.numel();
-        auto opts =
-            torch::TensorOptions().dtype(torch::kInt64).device(seeds.device());
-        auto counts = torch::empty({n}, opts);
-        qk::launch_capped_degree(stream, indptr_.data_ptr<int64_t>(),
-                                 seeds.data_ptr<int64_t>(), n, k,
-                                 counts.data_ptr<int64_t>());
-        auto [prefix, total] = exclusive_scan_total(counts, stream);
-        auto out = torch::empty({total}, opts);
-        auto ids = torch::empty({total}, opts);
-        qk::launch_rng_bump(stream, rng_dev(stream));
-        draw(stream, seeds.data_ptr<int64_t>(), n, k,
-             prefix.data_ptr<int64_t>(), out.data_ptr<int64_t>(),
-             ids.data_ptr<int64_t>(), 0, nullptr);
-        return {out, counts, ids};
+        return sample_impl(seeds, k, true);
     }
 
     // Negative tails for link prediction: (neg int64 [n, num_neg], ok bool
@@ -340,24 +282,8 @@ class GpuSampler {
     // sorted by time); placed like `indices`.
     void set_edge_time(torch::Tensor time_csr) {
         DeviceScope g(device_);
-        TORCH_CHECK(time_csr.dtype() == torch::kInt64,
-                    "edge times must be int64");
-        TORCH_CHECK(time_csr.dim() == 1 &&
-                        time_csr.numel() == indices_.numel(),
-                    "edge times: one per CSR slot expected");
-        if (dma_) {
-            time_ = time_csr.contiguous().to(
-                torch::Device(torch::kCUDA, device_));
-            time_dptr_ = time_.data_ptr<int64_t>();
-        } else {
-            TORCH_CHECK(time_csr.device().is_cpu(),
-                        "UVA mode expects CPU edge times");
-            time_ = pin_host(time_csr.contiguous());
-            // an empty graph has nothing to pin; the pointer is never read
-            time_dptr_ = time_.numel() == 0
-                ? indptr_.data_ptr<int64_t>()
-                : (int64_t*)host_devptr(time_);
-        }
+        std::tie(time_, time_dptr_) =
+            place_column<int64_t>(time_csr, "edge times", indices_.numel());
     }
 
     // One hop of temporal sampling over composite keys root * node_count +
@@ -415,42 +341,26 @@ class GpuSampler {
         int64_t n = seeds.numel(), m = nbrs.numel();
         auto opts =
             torch::TensorOptions().dtype(torch::kInt64).device(seeds.device());
-        auto i32 = opts.dtype(torch::kInt32);
 
-        int64_t capacity = next_pow2(2 * (n + m) + 64);
-        auto keys = torch::empty({capacity}, opts);
-        auto pos = torch::empty({capacity}, i32);
-        auto local = torch::empty({capacity}, i32);
-        qk::launch_reindex_init(stream, keys.data_ptr<int64_t>(),
-                                pos.data_ptr<int32_t>(), capacity);
-        qk::launch_hash_insert(stream, keys.data_ptr<int64_t>(),
-                               pos.data_ptr<int32_t>(), capacity,
-                               seeds.data_ptr<int64_t>(), n,
-                               nbrs.data_ptr<int64_t>(), m);
-        auto flags = torch::empty({n + m}, opts);
-        qk::launch_mark_first(stream, keys.data_ptr<int64_t>(),
-                              pos.data_ptr<int32_t>(), capacity,
-                              seeds.data_ptr<int64_t>(), n,
-                              nbrs.data_ptr<int64_t>(), m,
-                              flags.data_ptr<int64_t>());
-        auto [scanned, unique_total] = exclusive_scan_total(flags, stream);
-        auto frontier = torch::empty({unique_total}, opts);
-        qk::launch_compact_unique(
-            stream, keys.data_ptr<int64_t>(), local.data_ptr<int32_t>(),
-            pos.data_ptr<int32_t>(), capacity, seeds.data_ptr<int64_t>(), n,
-            nbrs.data_ptr<int64_t>(), m, scanned.data_ptr<int64_t>(),
-            flags.data_ptr<int64_t>(), frontier.data_ptr<int64_t>());
+        // both totals (unique nodes, sum of counts) come back in one copy:
+        // the one host sync, needed to size the outputs exactly
+        auto totals = torch::empty({2}, opts);
+        int64_t* td = totals.data_ptr<int64_t>();
+        auto table = reindex_build(stream, seeds.data_ptr<int64_t>(), n,
+                                   nbrs.data_ptr<int64_t>(), m, nullptr,
+                                   nullptr, td, opts);
+        auto prefix = exclusive_scan(counts, td + 1, stream);
+        auto totals_host = totals.cpu();
+        const int64_t* th = totals_host.data_ptr<int64_t>();
+        TORCH_CHECK(th[1] == m, "reindex: counts do not sum to neighbors");
+        auto frontier = torch::empty({th[0]}, opts);
         auto col_idx = torch::empty({m}, opts);
-        qk::launch_lookup_local(stream, keys.data_ptr<int64_t>(),
-                                local.data_ptr<int32_t>(), capacity,
-                                nbrs.data_ptr<int64_t>(), m,
-                                col_idx.data_ptr<int64_t>());
-        auto [prefix, total] = exclusive_scan_total(counts, stream);
-        TORCH_CHECK(total == m, "reindex: counts do not sum to neighbors");
         auto row_idx = torch::empty({m}, opts);
-        qk::launch_expand_rows(stream, prefix.data_ptr<int64_t>(),
-                               counts.data_ptr<int64_t>(), n,
-                               row_idx.data_ptr<int64_t>());
+        reindex_finish(stream, table, prefix.data_ptr<int64_t>(),
+                       counts.data_ptr<int64_t>(),
+                       frontier.data_ptr<int64_t>(),
+                       col_idx.data_ptr<int64_t>(),
+                       row_idx.data_ptr<int64_t>());
         return {frontier, row_idx, col_idx};
     }
 
@@ -492,7 +402,6 @@ class GpuSampler {
         for (int k : ks) TORCH_CHECK(k >= 1, "sample_hops: fanouts must be >=1");
         auto opts =
             torch::TensorOptions().dtype(torch::kInt64).device(seeds.device());
-        auto i32 = opts.dtype(torch::kInt32);
 
         auto sizes_dev = torch::empty({2 * H}, opts);
         int64_t* sd = sizes_dev.data_ptr<int64_t>();
@@ -504,7 +413,6 @@ class GpuSampler {
         const int64_t* n_dev = nullptr;     // exact frontier count (device)
         int64_t n_ub = seeds.numel();       // upper bound (host)
         std::vector<torch::Tensor> frontiers, hop_edges, dst_ptrs;
-        std::vector<int64_t> n_ubs;
 
         for (int h = 0; h < H; ++h) {
             const int k = ks[h];
@@ -518,13 +426,9 @@ class GpuSampler {
                                      cur.data_ptr<int64_t>(), n_ub, k,
                                      counts.data_ptr<int64_t>(), n_dev,
                                      /*zero_extra_slot=*/true);
-            auto prefix = torch::empty({n_ub + 1}, opts);
-            auto temp = torch::empty({(int64_t)qk::scan_temp_bytes(n_ub + 1)},
-                                     opts.dtype(torch::kUInt8));
-            qk::launch_exclusive_scan(stream, temp.data_ptr(), temp.numel(),
-                                      counts.data_ptr<int64_t>(),
-                                      prefix.data_ptr<int64_t>(), n_ub + 1,
-                                      sd + 2 * h);  // m_h
+            int64_t* m_dev = sd + 2 * h;      // m_h
+            int64_t* u_dev = sd + 2 * h + 1;  // unique_h
+            auto prefix = exclusive_scan(counts, m_dev, stream);
             auto out = torch::empty({m_ub}, opts);
             // edges[0] = col (src local), edges[1] = row (dst local):
             // the finished edge_index, written in place by the kernels;
@@ -539,55 +443,22 @@ class GpuSampler {
                  prefix.data_ptr<int64_t>(), out.data_ptr<int64_t>(), idp,
                  salt, n_dev);
 
-            // reindex [cur ++ out] -> frontier + local col ids
+            // reindex [cur ++ out] -> frontier + local col ids; the row
+            // prefix is the degree scan above
             const int64_t total_ub = n_ub + m_ub;
-            const int64_t capacity = next_pow2(2 * total_ub + 64);
-            auto keys = torch::empty({capacity}, opts);
-            auto pos = torch::empty({capacity}, i32);
-            auto local = torch::empty({capacity}, i32);
-            qk::launch_reindex_init(stream, keys.data_ptr<int64_t>(),
-                                    pos.data_ptr<int32_t>(), capacity);
-            qk::launch_hash_insert(stream, keys.data_ptr<int64_t>(),
-                                   pos.data_ptr<int32_t>(), capacity,
-                                   cur.data_ptr<int64_t>(), n_ub,
-                                   out.data_ptr<int64_t>(), m_ub, n_dev,
-                                   sd + 2 * h);
-            auto flags = torch::empty({total_ub}, opts);
-            qk::launch_mark_first(stream, keys.data_ptr<int64_t>(),
-                                  pos.data_ptr<int32_t>(), capacity,
-                                  cur.data_ptr<int64_t>(), n_ub,
-                                  out.data_ptr<int64_t>(), m_ub,
-                                  flags.data_ptr<int64_t>(), n_dev,
-                                  sd + 2 * h);
-            auto scanned = torch::empty({total_ub}, opts);
-            auto temp2 = torch::empty(
-                {(int64_t)qk::scan_temp_bytes(total_ub)},
-                opts.dtype(torch::kUInt8));
-            qk::launch_exclusive_scan(stream, temp2.data_ptr(), temp2.numel(),
-                                      flags.data_ptr<int64_t>(),
-                                      scanned.data_ptr<int64_t>(), total_ub,
-                                      sd + 2 * h + 1);  // unique_h
+            auto table = reindex_build(stream, cur.data_ptr<int64_t>(), n_ub,
+                                       out.data_ptr<int64_t>(), m_ub, n_dev,
+                                       m_dev, u_dev, opts);
             auto frontier = torch::zeros({total_ub}, opts);
-            qk::launch_compact_unique(
-                stream, keys.data_ptr<int64_t>(), local.data_ptr<int32_t>(),
-                pos.data_ptr<int32_t>(), capacity, cur.data_ptr<int64_t>(),
-                n_ub, out.data_ptr<int64_t>(), m_ub,
-                scanned.data_ptr<int64_t>(), flags.data_ptr<int64_t>(),
-                frontier.data_ptr<int64_t>(), n_dev, sd + 2 * h);
-            qk::launch_lookup_local(stream, keys.data_ptr<int64_t>(),
-                                    local.data_ptr<int32_t>(), capacity,
-                                    out.data_ptr<int64_t>(), m_ub,
-                                    colp, sd + 2 * h);
-            qk::launch_expand_rows(stream, prefix.data_ptr<int64_t>(),
-                                   counts.data_ptr<int64_t>(), n_ub,
-                                   rowp, n_dev);
+            reindex_finish(stream, table, prefix.data_ptr<int64_t>(),
+                           counts.data_ptr<int64_t>(),
+                           frontier.data_ptr<int64_t>(), colp, rowp);
 
             frontiers.push_back(frontier);
             hop_edges.push_back(edges);
             dst_ptrs.push_back(prefix);
-            n_ubs.push_back(n_ub);
             cur = frontier;
-            n_dev = sd + 2 * h + 1;
+            n_dev = u_dev;
             n_ub = total_ub;
         }
 
@@ -617,14 +488,6 @@ class GpuSampler {
         return res;
     }
 
-    std::vector<std::tuple<torch::Tensor, torch::Tensor>>
-    sample_hops(torch::Tensor seeds, const std::vector<int>& ks) {
-        std::vector<std::tuple<torch::Tensor, torch::Tensor>> res;
-        for (auto& [frontier, edges, ptr] : sample_hops_ptr(seeds, ks))
-            res.emplace_back(frontier, edges);
-        return res;
-    }
-
     void cal_neighbor_prob(int /*stream_id*/, torch::Tensor last_prob,
                            torch::Tensor cur_prob, int k) {
         DeviceScope g(device_);
@@ -639,6 +502,104 @@ class GpuSampler {
     int device() const { return device_; }
 
   private:
+    // A per-edge (CSR-aligned) column, placed where the kernels read it:
+    // a copy in HBM in DMA mode; in UVA mode (ZERO_COPY) pinned host memory
+    // read over PCIe, which keeps graphs larger than HBM samplable.
+    // Returns the held tensor and its device-visible pointer.
+    template <typename T>
+    std::pair<torch::Tensor, T*> place_column(const torch::Tensor& col,
+                                              const char* name, int64_t len) {
+        TORCH_CHECK(col.scalar_type() == torch::CppTypeToScalarType<T>::value,
+                    name, " must be ",
+                    std::is_same<T, float>::value ? "float32" : "int64");
+        TORCH_CHECK(col.dim() == 1 && col.numel() == len, name,
+                    ": one per CSR slot expected");
+        torch::Tensor held;
+        if (dma_) {
+            held = col.contiguous().to(torch::Device(torch::kCUDA, device_));
+        } else {
+            TORCH_CHECK(col.device().is_cpu(), "UVA mode expects CPU ", name);
+            held = pin_host(col.contiguous());
+        }
+        // an empty graph has nothing to pin; the pointer is never read
+        if (len == 0) return {held, (T*)indptr_.data_ptr()};
+        return {held, dma_ ? held.data_ptr<T>() : (T*)host_devptr(held)};
+    }
+
+    // sample_neighbor[_eid]: (out, counts, ids), ids empty unless wanted.
+    // One host sync, for the total.
+    std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> sample_impl(
+        torch::Tensor seeds, int k, bool want_ids) {
+        DeviceScope g(device_);
+        auto stream = current_stream();
+        seeds = seeds.contiguous();
+        TORCH_CHECK(seeds.device().is_cuda(), "seeds must be on GPU");
+        int64_t n = seeds.numel();
+        auto opts =
+            torch::TensorOptions().dtype(torch::kInt64).device(seeds.device());
+        auto counts = torch::empty({n}, opts);
+        qk::launch_capped_degree(stream, indptr_.data_ptr<int64_t>(),
+                                 seeds.data_ptr<int64_t>(), n, k,
+                                 counts.data_ptr<int64_t>());
+        auto [prefix, total] = exclusive_scan_total(counts, stream);
+        auto out = torch::empty({total}, opts);
+        auto ids = torch::empty({want_ids ? total : 0}, opts);
+        qk::launch_rng_bump(stream, rng_dev(stream));
+        draw(stream, seeds.data_ptr<int64_t>(), n, k,
+             prefix.data_ptr<int64_t>(), out.data_ptr<int64_t>(),
+             want_ids ? ids.data_ptr<int64_t>() : nullptr, 0, nullptr);
+        return {out, counts, ids};
+    }
+
+    // The frontier reindex of [seeds ++ nbrs], in two steps so that a
+    // caller may read the unique count before it sizes the frontier.
+    // n_seeds/n_nbrs are host upper bounds that size the buffers and the
+    // grids; n_seeds_dev/n_nbrs_dev, when non-null, are the exact counts
+    // on the device.  Everything is enqueued on `stream` with no host sync.
+    struct ReindexTable {
+        torch::Tensor keys, pos, local, flags, scanned;
+        qk::ReindexSet set;
+    };
+
+    // Step 1: init, insert, mark_first, scan.  *unique_dev (device)
+    // receives the number of distinct ids.
+    ReindexTable reindex_build(hipStream_t stream, const int64_t* seeds,
+                               int64_t n_seeds, const int64_t* nbrs,
+                               int64_t n_nbrs, const int64_t* n_seeds_dev,
+                               const int64_t* n_nbrs_dev, int64_t* unique_dev,
+                               const torch::TensorOptions& opts) {
+        ReindexTable t;
+        // load factor <= 1/2 keeps the linear probes short
+        const int64_t capacity = next_pow2(2 * (n_seeds + n_nbrs) + 64);
+        auto i32 = opts.dtype(torch::kInt32);
+        t.keys = torch::empty({capacity}, opts);
+        t.pos = torch::empty({capacity}, i32);
+        t.local = torch::empty({capacity}, i32);
+        t.set = {t.keys.data_ptr<int64_t>(), t.pos.data_ptr<int32_t>(),
+                 t.local.data_ptr<int32_t>(), capacity, seeds, n_seeds, nbrs,
+                 n_nbrs, n_seeds_dev, n_nbrs_dev};
+        qk::launch_reindex_init(stream, t.set.keys, t.set.pos, capacity);
+        qk::launch_hash_insert(stream, t.set);
+        t.flags = torch::empty({n_seeds + n_nbrs}, opts);
+        qk::launch_mark_first(stream, t.set, t.flags.data_ptr<int64_t>());
+        t.scanned = exclusive_scan(t.flags, unique_dev, stream);
+        return t;
+    }
+
+    // Step 2: compact, lookup, expand_rows.  frontier holds at least the
+    // unique count; col/row hold n_nbrs; prefix/counts are the per-seed
+    // neighbor counts and their exclusive scan.
+    void reindex_finish(hipStream_t stream, const ReindexTable& t,
+                        const int64_t* prefix, const int64_t* counts,
+                        int64_t* frontier, int64_t* col, int64_t* row) {
+        qk::launch_compact_unique(stream, t.set,
+                                  t.scanned.data_ptr<int64_t>(),
+                                  t.flags.data_ptr<int64_t>(), frontier);
+        qk::launch_lookup_local(stream, t.set, col);
+        qk::launch_expand_rows(stream, prefix, counts, t.set.n_seeds, row,
+                               t.set.n_seeds_dev);
+    }
+
     // The one draw of every sampling path: uniform (launch_sample, as
     // ever) unless edge weights were set.  out_eids may be null.
     void draw(hipStream_t stream, const int64_t* seeds, int64_t n, int k,
@@ -675,7 +636,6 @@ class GpuSampler {
 
     int device_;
     bool dma_;
-    bool has_eid_ = false;
     int64_t node_count_ = 0;
     torch::Tensor indptr_, indices_, eid_;
     int64_t* indices_dptr_ = nullptr;
@@ -2465,12 +2425,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              py::call_guard<py::gil_scoped_release>(),
              "one hop over keys root * node_count + node, edges with time "
              "<= seed_time[root] only: (out_keys, counts, eids)")
-        .def("sample_hops", &GpuSampler::sample_hops,
-             py::call_guard<py::gil_scoped_release>(),
-             "fused multi-hop sample+reindex, one sync per batch")
         .def("sample_hops_ptr", &GpuSampler::sample_hops_ptr,
              py::call_guard<py::gil_scoped_release>(),
-             "sample_hops plus each hop's dst segment pointer")
+             "fused multi-hop sample+reindex, one sync per batch: per hop "
+             "(frontier, edge_index, dst segment pointer)")
         .def("sample_hops_raw", &GpuSampler::sample_hops_raw,
              py::call_guard<py::gil_scoped_release>(),
              "zero-sync variant: ub-sized tensors + device sizes vector")

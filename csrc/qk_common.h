@@ -148,36 +148,30 @@ void launch_cal_next(hipStream_t s, const int64_t* indptr,
 
 // ---------- reindex (reindex_kernels.hip) ----------
 
-// Open-addressing hash table working set; all buffers caller-allocated.
-//   capacity: power of two >= 2*(n_seeds+n_nbrs)
-//   keys:   int64[capacity]  (pre-filled with -1 by launch_reindex_init)
-//   pos:    int32[capacity]
-//   local:  int32[capacity]
-//   flags/scan: int64[n_seeds+n_nbrs]
+// Open-addressing hash table working set over [seeds ++ nbrs]; all buffers
+// caller-allocated.  flags/scan are int64[n_seeds+n_nbrs].
+struct ReindexSet {
+    int64_t* keys;     // int64[capacity], -1-filled by launch_reindex_init
+    int32_t* pos;      // int32[capacity]
+    int32_t* local;    // int32[capacity]
+    int64_t capacity;  // power of two >= 2*(n_seeds+n_nbrs)
+    const int64_t* seeds;
+    int64_t n_seeds;   // host bound: sizes the grid and the buffers
+    const int64_t* nbrs;
+    int64_t n_nbrs;
+    // exact counts on the device (dynamic-count convention as above);
+    // null = the host bound is exact
+    const int64_t* n_seeds_dev = nullptr;
+    const int64_t* n_nbrs_dev = nullptr;
+};
 void launch_reindex_init(hipStream_t s, int64_t* keys, int32_t* pos,
                          int64_t capacity);
-void launch_hash_insert(hipStream_t s, int64_t* keys, int32_t* pos,
-                        int64_t capacity, const int64_t* seeds, int64_t n_seeds,
-                        const int64_t* nbrs, int64_t n_nbrs,
-                        const int64_t* n_seeds_dev = nullptr,
-                        const int64_t* n_nbrs_dev = nullptr);
-void launch_mark_first(hipStream_t s, const int64_t* keys, const int32_t* pos,
-                       int64_t capacity, const int64_t* seeds, int64_t n_seeds,
-                       const int64_t* nbrs, int64_t n_nbrs, int64_t* flags,
-                       const int64_t* n_seeds_dev = nullptr,
-                       const int64_t* n_nbrs_dev = nullptr);
-void launch_compact_unique(hipStream_t s, const int64_t* keys, int32_t* local,
-                           const int32_t* pos, int64_t capacity,
-                           const int64_t* seeds, int64_t n_seeds,
-                           const int64_t* nbrs, int64_t n_nbrs,
+void launch_hash_insert(hipStream_t s, const ReindexSet& w);
+void launch_mark_first(hipStream_t s, const ReindexSet& w, int64_t* flags);
+void launch_compact_unique(hipStream_t s, const ReindexSet& w,
                            const int64_t* scanned_flags, const int64_t* flags,
-                           int64_t* out_nodes,
-                           const int64_t* n_seeds_dev = nullptr,
-                           const int64_t* n_nbrs_dev = nullptr);
-void launch_lookup_local(hipStream_t s, const int64_t* keys,
-                         const int32_t* local, int64_t capacity,
-                         const int64_t* nbrs, int64_t n_nbrs, int64_t* col_idx,
-                         const int64_t* n_nbrs_dev = nullptr);
+                           int64_t* out_nodes);
+void launch_lookup_local(hipStream_t s, const ReindexSet& w, int64_t* col_idx);
 // row_idx[prefix[i]+j] = i  for j < counts[i]
 void launch_expand_rows(hipStream_t s, const int64_t* prefix,
                         const int64_t* counts, int64_t n_seeds,

@@ -55,26 +55,30 @@ __global__ void init_kernel(int64_t* keys, int32_t* pos, int64_t capacity) {
     }
 }
 
-__global__ void insert_kernel(int64_t* keys, int32_t* pos, int64_t capacity,
-                              const int64_t* seeds, int64_t n_seeds,
-                              const int64_t* nbrs, int64_t total,
-                              const int64_t* n_seeds_dev,
-                              const int64_t* n_nbrs_dev) {
-    const int64_t nn = n_seeds_dev ? *n_seeds_dev : n_seeds;
-    const int64_t tt = n_nbrs_dev ? nn + *n_nbrs_dev : total;
+// Exact counts of the working set: the device counts if given, else the
+// host bounds.  *nn = seeds, *tt = seeds + neighbors.
+__device__ __forceinline__ void live_counts(const ReindexSet& w, int64_t* nn,
+                                            int64_t* tt) {
+    *nn = w.n_seeds_dev ? *w.n_seeds_dev : w.n_seeds;
+    *tt = w.n_nbrs_dev ? *nn + *w.n_nbrs_dev : w.n_seeds + w.n_nbrs;
+}
+
+__global__ void insert_kernel(ReindexSet w) {
+    int64_t nn, tt;
+    live_counts(w, &nn, &tt);
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    int64_t mask = capacity - 1;
+    int64_t mask = w.capacity - 1;
     for (; i < tt; i += stride) {
         int64_t key;
-        combined_at(seeds, nn, nbrs, i, &key);
+        combined_at(w.seeds, nn, w.nbrs, i, &key);
         int64_t slot = (int64_t)(hash64((uint64_t)key) & (uint64_t)mask);
         while (true) {
             int64_t prev = atomicCAS(
-                reinterpret_cast<unsigned long long*>(&keys[slot]),
+                reinterpret_cast<unsigned long long*>(&w.keys[slot]),
                 (unsigned long long)(-1LL), (unsigned long long)key);
             if (prev == -1 || prev == key) {
-                atomicMin(&pos[slot], (int32_t)i);
+                atomicMin(&w.pos[slot], (int32_t)i);
                 break;
             }
             slot = (slot + 1) & mask;
@@ -82,14 +86,10 @@ __global__ void insert_kernel(int64_t* keys, int32_t* pos, int64_t capacity,
     }
 }
 
-__global__ void mark_first_kernel(const int64_t* keys, const int32_t* pos,
-                                  int64_t capacity, const int64_t* seeds,
-                                  int64_t n_seeds, const int64_t* nbrs,
-                                  int64_t total, int64_t* flags,
-                                  const int64_t* n_seeds_dev,
-                                  const int64_t* n_nbrs_dev) {
-    const int64_t nn = n_seeds_dev ? *n_seeds_dev : n_seeds;
-    const int64_t tt = n_nbrs_dev ? nn + *n_nbrs_dev : total;
+__global__ void mark_first_kernel(ReindexSet w, int64_t* flags) {
+    int64_t nn, tt;
+    live_counts(w, &nn, &tt);
+    const int64_t total = w.n_seeds + w.n_nbrs;
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (; i < total; i += stride) {
@@ -98,45 +98,36 @@ __global__ void mark_first_kernel(const int64_t* keys, const int32_t* pos,
             continue;
         }
         int64_t key;
-        combined_at(seeds, nn, nbrs, i, &key);
-        int64_t slot = probe_find(keys, capacity, key);
-        flags[i] = (slot >= 0 && pos[slot] == (int32_t)i) ? 1 : 0;
+        combined_at(w.seeds, nn, w.nbrs, i, &key);
+        int64_t slot = probe_find(w.keys, w.capacity, key);
+        flags[i] = (slot >= 0 && w.pos[slot] == (int32_t)i) ? 1 : 0;
     }
 }
 
-__global__ void compact_kernel(const int64_t* keys, int32_t* local,
-                               const int32_t* pos, int64_t capacity,
-                               const int64_t* seeds, int64_t n_seeds,
-                               const int64_t* nbrs, int64_t total,
-                               const int64_t* scanned, const int64_t* flags,
-                               int64_t* out_nodes,
-                               const int64_t* n_seeds_dev,
-                               const int64_t* n_nbrs_dev) {
-    const int64_t nn = n_seeds_dev ? *n_seeds_dev : n_seeds;
-    const int64_t tt = n_nbrs_dev ? nn + *n_nbrs_dev : total;
+__global__ void compact_kernel(ReindexSet w, const int64_t* scanned,
+                               const int64_t* flags, int64_t* out_nodes) {
+    int64_t nn, tt;
+    live_counts(w, &nn, &tt);
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (; i < tt; i += stride) {
         if (!flags[i]) continue;
         int64_t key;
-        combined_at(seeds, nn, nbrs, i, &key);
-        int64_t slot = probe_find(keys, capacity, key);
+        combined_at(w.seeds, nn, w.nbrs, i, &key);
+        int64_t slot = probe_find(w.keys, w.capacity, key);
         int64_t lid = scanned[i];
-        local[slot] = (int32_t)lid;
+        w.local[slot] = (int32_t)lid;
         out_nodes[lid] = key;
     }
 }
 
-__global__ void lookup_kernel(const int64_t* keys, const int32_t* local,
-                              int64_t capacity, const int64_t* nbrs,
-                              int64_t n_nbrs, int64_t* col_idx,
-                              const int64_t* n_nbrs_dev) {
-    const int64_t mm = n_nbrs_dev ? *n_nbrs_dev : n_nbrs;
+__global__ void lookup_kernel(ReindexSet w, int64_t* col_idx) {
+    const int64_t mm = w.n_nbrs_dev ? *w.n_nbrs_dev : w.n_nbrs;
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (; i < mm; i += stride) {
-        int64_t slot = probe_find(keys, capacity, nbrs[i]);
-        col_idx[i] = (int64_t)local[slot];
+        int64_t slot = probe_find(w.keys, w.capacity, w.nbrs[i]);
+        col_idx[i] = (int64_t)w.local[slot];
     }
 }
 
@@ -174,55 +165,34 @@ void launch_reindex_init(hipStream_t s, int64_t* keys, int32_t* pos,
     QK_CHECK_HIP(hipGetLastError());
 }
 
-void launch_hash_insert(hipStream_t s, int64_t* keys, int32_t* pos,
-                        int64_t capacity, const int64_t* seeds, int64_t n_seeds,
-                        const int64_t* nbrs, int64_t n_nbrs,
-                        const int64_t* n_seeds_dev,
-                        const int64_t* n_nbrs_dev) {
-    int64_t total = n_seeds + n_nbrs;
+void launch_hash_insert(hipStream_t s, const ReindexSet& w) {
+    int64_t total = w.n_seeds + w.n_nbrs;
     if (total == 0) return;
-    insert_kernel<<<grid_for(total, BLOCK), BLOCK, 0, s>>>(
-        keys, pos, capacity, seeds, n_seeds, nbrs, total, n_seeds_dev,
-        n_nbrs_dev);
+    insert_kernel<<<grid_for(total, BLOCK), BLOCK, 0, s>>>(w);
     QK_CHECK_HIP(hipGetLastError());
 }
 
-void launch_mark_first(hipStream_t s, const int64_t* keys, const int32_t* pos,
-                       int64_t capacity, const int64_t* seeds, int64_t n_seeds,
-                       const int64_t* nbrs, int64_t n_nbrs, int64_t* flags,
-                       const int64_t* n_seeds_dev,
-                       const int64_t* n_nbrs_dev) {
-    int64_t total = n_seeds + n_nbrs;
+void launch_mark_first(hipStream_t s, const ReindexSet& w, int64_t* flags) {
+    int64_t total = w.n_seeds + w.n_nbrs;
     if (total == 0) return;
-    mark_first_kernel<<<grid_for(total, BLOCK), BLOCK, 0, s>>>(
-        keys, pos, capacity, seeds, n_seeds, nbrs, total, flags, n_seeds_dev,
-        n_nbrs_dev);
+    mark_first_kernel<<<grid_for(total, BLOCK), BLOCK, 0, s>>>(w, flags);
     QK_CHECK_HIP(hipGetLastError());
 }
 
-void launch_compact_unique(hipStream_t s, const int64_t* keys, int32_t* local,
-                           const int32_t* pos, int64_t capacity,
-                           const int64_t* seeds, int64_t n_seeds,
-                           const int64_t* nbrs, int64_t n_nbrs,
+void launch_compact_unique(hipStream_t s, const ReindexSet& w,
                            const int64_t* scanned_flags, const int64_t* flags,
-                           int64_t* out_nodes,
-                           const int64_t* n_seeds_dev,
-                           const int64_t* n_nbrs_dev) {
-    int64_t total = n_seeds + n_nbrs;
+                           int64_t* out_nodes) {
+    int64_t total = w.n_seeds + w.n_nbrs;
     if (total == 0) return;
     compact_kernel<<<grid_for(total, BLOCK), BLOCK, 0, s>>>(
-        keys, local, pos, capacity, seeds, n_seeds, nbrs, total, scanned_flags,
-        flags, out_nodes, n_seeds_dev, n_nbrs_dev);
+        w, scanned_flags, flags, out_nodes);
     QK_CHECK_HIP(hipGetLastError());
 }
 
-void launch_lookup_local(hipStream_t s, const int64_t* keys,
-                         const int32_t* local, int64_t capacity,
-                         const int64_t* nbrs, int64_t n_nbrs,
-                         int64_t* col_idx, const int64_t* n_nbrs_dev) {
-    if (n_nbrs == 0) return;
-    lookup_kernel<<<grid_for(n_nbrs, BLOCK), BLOCK, 0, s>>>(
-        keys, local, capacity, nbrs, n_nbrs, col_idx, n_nbrs_dev);
+void launch_lookup_local(hipStream_t s, const ReindexSet& w,
+                         int64_t* col_idx) {
+    if (w.n_nbrs == 0) return;
+    lookup_kernel<<<grid_for(w.n_nbrs, BLOCK), BLOCK, 0, s>>>(w, col_idx);
     QK_CHECK_HIP(hipGetLastError());
 }
 

@@ -259,10 +259,9 @@ void test_reindex() {
     h2d(d_seeds, seeds);
     h2d(d_nbrs, nbrs);
     qk::launch_reindex_init(nullptr, d_keys, d_pos, cap);
-    qk::launch_hash_insert(nullptr, d_keys, d_pos, cap, d_seeds, n, d_nbrs,
-                           m);
-    qk::launch_mark_first(nullptr, d_keys, d_pos, cap, d_seeds, n, d_nbrs, m,
-                          d_flags);
+    qk::ReindexSet w{d_keys, d_pos, d_local, cap, d_seeds, n, d_nbrs, m};
+    qk::launch_hash_insert(nullptr, w);
+    qk::launch_mark_first(nullptr, w, d_flags);
     size_t tb = qk::scan_temp_bytes(n + m);
     void* d_temp = nullptr;
     QK_CHECK_HIP(hipMalloc(&d_temp, tb));
@@ -273,10 +272,9 @@ void test_reindex() {
     QK_CHECK_HIP(hipDeviceSynchronize());
     int64_t uniq = d2h(d_total, 1)[0];
     auto* d_frontier = dalloc<int64_t>(uniq);
-    qk::launch_compact_unique(nullptr, d_keys, d_local, d_pos, cap, d_seeds,
-                              n, d_nbrs, m, d_scan, d_flags, d_frontier);
+    qk::launch_compact_unique(nullptr, w, d_scan, d_flags, d_frontier);
     auto* d_col = dalloc<int64_t>(m);
-    qk::launch_lookup_local(nullptr, d_keys, d_local, cap, d_nbrs, m, d_col);
+    qk::launch_lookup_local(nullptr, w, d_col);
     QK_CHECK_HIP(hipDeviceSynchronize());
     auto frontier = d2h(d_frontier, uniq);
     auto col = d2h(d_col, m);

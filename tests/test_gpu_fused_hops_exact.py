@@ -198,6 +198,28 @@ def test_all_seeds_isolated(det, mode):
 
 
 @pytest.mark.parametrize("mode", MODES)
+def test_edgeless_graph(mode):
+    """Five nodes and no edge: every per-edge column the engine places
+    (indices, id map, times) is empty, and a batch is its seeds."""
+    indptr = torch.zeros(6, dtype=torch.int64)
+    none = torch.zeros(0, dtype=torch.int64)
+    topo = quiver.CSRTopo(indptr=indptr, indices=none)
+    seeds = torch.tensor([3, 0, 4])
+    model = fm.hops_model(indptr, none, seeds, FANOUTS)
+    assert model.sizes.tolist() == [0, 3, 0, 3]
+    s = quiver.GraphSageSampler(topo, FANOUTS, device=0, mode=mode,
+                                return_eid=True, edge_time=none)
+    n_id, _, adjs = s.sample(seeds)
+    _check_batch(model, n_id, adjs, seeds, with_eid=True)
+    token, (n_id, _, adjs) = _async(s, seeds)
+    _check_batch(model, n_id, adjs, seeds, with_eid=True)
+    _check_raw(model, token, seeds, FANOUTS)
+    bound = torch.zeros(3, dtype=torch.int64, device="cuda")
+    out, cnt, ids = s.quiver.sample_neighbor_temporal(seeds.cuda(), bound, 3)
+    assert out.numel() == 0 and ids.numel() == 0 and cnt.tolist() == [0, 0, 0]
+
+
+@pytest.mark.parametrize("mode", MODES)
 def test_duplicate_seeds(det, mode):
     """Repeated seeds: the first hop's dst ids are seed POSITIONS, its
     frontier holds each seed once."""
