@@ -224,6 +224,66 @@ def bench_temporal(mode, shape, topo, edge_time, batch=1024, iters=30,
     return res
 
 
+def torch_uniform_walk(indptr, indices, start, length):
+    """The only baseline there is: a uniform walk as `length` rounds of
+    torch index arithmetic on device-resident indptr / indices."""
+    last = indices.numel() - 1
+    cur, out = start, [start]
+    for _ in range(length):
+        live = cur >= 0
+        at = cur.clamp(min=0)
+        beg = indptr[at]
+        deg = indptr[at + 1] - beg
+        r = (torch.rand(cur.numel(), device=cur.device,
+                        dtype=torch.float64) * deg).long()
+        nxt = indices[(beg + r).clamp(max=last)]
+        cur = torch.where(live & (deg > 0), nxt, torch.full_like(nxt, -1))
+        out.append(cur)
+    return torch.stack(out, 1)
+
+
+def bench_walk(mode, shape, topo, p, q, length=20, batches=(1024, 65536),
+               iters=20, repeats=7, warmup=3, device=0):
+    """random_walk: uniform walks and (p, q) walks of `length` steps for
+    each batch size, and in GPU mode the plain-torch uniform walk on the
+    same starts (it needs the CSR in HBM, so UVA mode has no baseline).
+    Each repeat times `iters` calls of each in turn, over `iters` different
+    start sets; reported are the median and the min..max over the repeats
+    in ms per call, and walk steps per second at the median."""
+    cfg = SHAPES[shape]
+    sampler = quiver.GraphSageSampler(topo, cfg["fanout"], device=device,
+                                      mode=mode)
+    dev = f"cuda:{device}"
+    sync = torch.cuda.synchronize
+    res = dict(mode=mode, shape=shape, walk=True, walk_length=length, p=p,
+               q=q, iters=iters, repeats=repeats, batches={})
+    if mode == "GPU":
+        d_indptr, d_indices = topo.indptr.to(dev), topo.indices.to(dev)
+    g = torch.Generator().manual_seed(7)
+    for batch in batches:
+        starts = [torch.randint(0, cfg["train"], (batch,), generator=g)
+                  .to(dev) for _ in range(iters)]
+        parts = dict(
+            uniform=lambda s: sampler.random_walk(s, length),
+            node2vec=lambda s: sampler.random_walk(s, length, p, q))
+        if mode == "GPU":
+            parts["torch_uniform"] = lambda s: torch_uniform_walk(
+                d_indptr, d_indices, s, length)
+        for fn in parts.values():
+            _timed(fn, starts[:warmup], sync)
+        ms = {k: [] for k in parts}
+        for _ in range(repeats):
+            for k, fn in parts.items():
+                ms[k].append(_timed(fn, starts, sync))
+        cell = {}
+        for k, v in ms.items():
+            cell[k + "_ms"] = _stats(v)
+            cell[k + "_steps_per_s"] = \
+                batch * length / (float(np.median(v)) * 1e-3)
+        res["batches"][str(batch)] = cell
+    return res
+
+
 if __name__ == "__main__":
     p = argparse.ArgumentParser()
     p.add_argument("--modes", default="UVA,GPU,CPU")
@@ -248,7 +308,28 @@ if __name__ == "__main__":
                    help="time sample_temporal (synthetic edge times, seeds "
                         "bounded at the median) beside plain sample(); with "
                         "--links also temporal sample_links")
+    p.add_argument("--walk", action="store_true",
+                   help="time random_walk (uniform and --p/--q walks, B = "
+                        "1024 and 65536) in GPU and UVA mode, beside a "
+                        "plain-torch uniform walk in GPU mode")
+    p.add_argument("--p", type=float, default=0.5)
+    p.add_argument("--q", type=float, default=2.0)
+    p.add_argument("--walk-length", type=int, default=20)
     args = p.parse_args()
+    if args.walk:
+        assert torch.cuda.is_available(), "--walk needs a GPU"
+        for shape in args.shapes.split(","):
+            cfg = SHAPES[shape]
+            indptr, indices = make_graph(cfg["nodes"], cfg["edges"])
+            topo = quiver.CSRTopo(indptr=indptr, indices=indices)
+            for mode in args.modes.split(","):
+                if mode == "CPU":       # the walks are timed on the GPU
+                    continue
+                print(json.dumps(bench_walk(
+                    mode, shape, topo, args.p, args.q,
+                    length=args.walk_length, iters=min(args.iters, 20),
+                    repeats=args.repeats)), flush=True)
+        sys.exit(0)
     if args.temporal:
         for shape in args.shapes.split(","):
             cfg = SHAPES[shape]

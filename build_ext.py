@@ -28,11 +28,12 @@ KERNEL_SOURCES = [
 ]
 TORCH_SOURCES = ["module.cpp"]
 HEADERS = ["qk_common.h", "segment_io.h"]
-# per-file extra flags.  gatv2: keep the compiler from pairing fp32 math
-# into packed two-wide instructions (scalar fp32 ops only).
+# per-file extra flags.  gatv2, sample: keep the compiler from pairing fp32
+# math into packed two-wide instructions (scalar fp32 ops only).
+NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
-    "gatv2_kernels.hip": ["-Xclang", "-target-feature",
-                          "-Xclang", "-packed-fp32-ops"],
+    "gatv2_kernels.hip": NO_PACKED_FP32,
+    "sample_kernels.hip": NO_PACKED_FP32,
 }
 OUT = os.path.join(ROOT, "torch_quiver.so")
 

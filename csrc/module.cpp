@@ -277,6 +277,43 @@ class GpuSampler {
         return {neg, ok};
     }
 
+    // Random walks from `start`: (walk int64 [n, walk_length + 1], e_id
+    // int64 [n, walk_length], or [n, 0] unless edge ids are emitted),
+    // contract at launch_random_walk.  All sizes are known on the host: no
+    // sync, one launch plus the seed bump.
+    std::tuple<torch::Tensor, torch::Tensor> random_walk(
+        torch::Tensor start, int walk_length, double p, double q,
+        int max_tries) {
+        DeviceScope g(device_);
+        auto stream = current_stream();
+        TORCH_CHECK(start.dtype() == torch::kInt64, "start must be int64");
+        TORCH_CHECK(start.device().is_cuda() &&
+                        start.device().index() == device_,
+                    "start must be on the sampler's GPU");
+        TORCH_CHECK(start.dim() == 1 && start.is_contiguous(),
+                    "start must be a contiguous 1-D tensor");
+        TORCH_CHECK(walk_length >= 1, "walk_length must be >= 1");
+        TORCH_CHECK(std::isfinite(p) && p > 0 && std::isfinite(q) && q > 0,
+                    "p and q must be finite and > 0");
+        TORCH_CHECK(max_tries >= 16, "max_tries must be >= 16");
+        TORCH_CHECK(!weight_dptr_,
+                    "random_walk: there is no edge-weighted walk");
+        const int64_t n = start.numel();
+        auto walk = torch::empty({n, (int64_t)walk_length + 1},
+                                 start.options());
+        auto ids = torch::empty({n, emit_eid_ ? (int64_t)walk_length : 0},
+                                start.options());
+        if (n == 0) return {walk, ids};
+        qk::launch_rng_bump(stream, rng_dev(stream));
+        qk::launch_random_walk(
+            stream, indptr_.data_ptr<int64_t>(), indices_dptr_, eid_dptr_,
+            start.data_ptr<int64_t>(), n, walk_length, node_count_, p, q,
+            max_tries, walk.data_ptr<int64_t>(),
+            emit_eid_ ? ids.data_ptr<int64_t>() : nullptr, 0,
+            rng_dev(stream));
+        return {walk, ids};
+    }
+
     // Opt-in edge times for sample_neighbor_temporal: one int64 per CSR
     // slot, every row ascending (the caller built the engine from rows
     // sorted by time); placed like `indices`.
@@ -926,6 +963,103 @@ class CpuSampler {
         return {neg, ok};
     }
 
+    // The seed of random_walk, which draws from stateless streams keyed by
+    // (seed, walk row, step) like the GPU engine, so a call does not depend
+    // on how its walks are spread over threads.  The other draws of this
+    // engine keep their per-thread generators.
+    void set_seed(uint64_t seed) { walk_seed_.store(seed); }
+
+    // Random walks, the contract of launch_random_walk: (walk int64 [n,
+    // walk_length + 1], e_id int64 [n, walk_length], or [n, 0] unless
+    // `want_ids`).  Every second-order step is drawn from its exact
+    // distribution: each neighbour of the current node is classified by a
+    // linear search of the previous node's row.  No rejection, so
+    // `max_tries` is accepted and ignored.
+    std::tuple<torch::Tensor, torch::Tensor> random_walk(
+        torch::Tensor start, int walk_length, double p, double q,
+        int /*max_tries*/, bool want_ids) {
+        TORCH_CHECK(start.dtype() == torch::kInt64, "start must be int64");
+        TORCH_CHECK(start.device().is_cpu(), "start must be a CPU tensor");
+        TORCH_CHECK(start.dim() == 1 && start.is_contiguous(),
+                    "start must be a contiguous 1-D tensor");
+        TORCH_CHECK(walk_length >= 1, "walk_length must be >= 1");
+        TORCH_CHECK(std::isfinite(p) && p > 0 && std::isfinite(q) && q > 0,
+                    "p and q must be finite and > 0");
+        TORCH_CHECK(!weight_.defined(),
+                    "random_walk: there is no edge-weighted walk");
+        const int64_t n = start.numel(), L = walk_length;
+        const int64_t* sp = start.data_ptr<int64_t>();
+        const int64_t* indptr = indptr_.data_ptr<int64_t>();
+        const int64_t* indices = indices_.data_ptr<int64_t>();
+        const int64_t* eid = eid_.defined() ? eid_.data_ptr<int64_t>()
+                                            : nullptr;
+        auto walk = torch::empty({n, L + 1}, start.options());
+        auto ids = torch::empty({n, want_ids ? L : 0}, start.options());
+        int64_t* wp = walk.data_ptr<int64_t>();
+        int64_t* ip = want_ids ? ids.data_ptr<int64_t>() : nullptr;
+        const uint64_t seed =
+            walk_seed_.fetch_add(0x9e3779b97f4a7c15ULL) +
+            0x9e3779b97f4a7c15ULL;
+        const bool first_order = p == 1.0 && q == 1.0;
+        const double inv_p = 1.0 / p, inv_q = 1.0 / q;
+        auto hash = [](uint64_t x) {            // SplitMix64
+            x += 0x9e3779b97f4a7c15ULL;
+            x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ULL;
+            x = (x ^ (x >> 27)) * 0x94d049bb133111ebULL;
+            return x ^ (x >> 31);
+        };
+        at::parallel_for(0, n, 16, [&](int64_t b, int64_t e) {
+            std::vector<double> cum;
+            for (int64_t i = b; i < e; ++i) {
+                int64_t v = sp[i], prev = -1;
+                wp[i * (L + 1)] = v;
+                if (v < 0 || v >= node_count_) v = -1;
+                const uint64_t base =
+                    seed + (uint64_t)i * 0x9e3779b97f4a7c15ULL;
+                for (int64_t t = 0; t < L; ++t) {
+                    int64_t nxt = -1, id = -1;
+                    const int64_t beg = v < 0 ? 0 : indptr[v];
+                    const int64_t deg = v < 0 ? 0 : indptr[v + 1] - beg;
+                    if (deg > 0) {
+                        const uint64_t h = hash(
+                            base + (uint64_t)t * 0x632be59bd9b4e019ULL);
+                        int64_t at;
+                        if (first_order || prev < 0) {
+                            // exact for any row length: the high half of
+                            // the 128-bit product
+                            at = (int64_t)(((unsigned __int128)h *
+                                            (uint64_t)deg) >> 64);
+                        } else {
+                            const int64_t* pb = indices + indptr[prev];
+                            const int64_t* pe = indices + indptr[prev + 1];
+                            cum.resize(deg);
+                            double total = 0;
+                            for (int64_t j = 0; j < deg; ++j) {
+                                const int64_t x = indices[beg + j];
+                                total += x == prev ? inv_p
+                                         : std::find(pb, pe, x) != pe
+                                             ? 1.0 : inv_q;
+                                cum[j] = total;
+                            }
+                            const double u =
+                                (double)(h >> 11) * 0x1p-53 * total;
+                            at = std::upper_bound(cum.begin(), cum.end(), u)
+                                 - cum.begin();
+                            if (at >= deg) at = deg - 1;    // rounding
+                        }
+                        nxt = indices[beg + at];
+                        id = eid ? eid[beg + at] : beg + at;
+                    }
+                    wp[i * (L + 1) + t + 1] = nxt;
+                    if (ip) ip[i * L + t] = id;
+                    prev = v;
+                    v = nxt;
+                }
+            }
+        });
+        return {walk, ids};
+    }
+
     std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> reindex_single(
         torch::Tensor seeds, torch::Tensor nbrs, torch::Tensor counts) {
         seeds = seeds.contiguous().cpu();
@@ -970,6 +1104,7 @@ class CpuSampler {
     torch::Tensor indptr_, indices_, eid_, weight_, time_;
     bool emit_eid_ = false;
     int64_t node_count_;
+    std::atomic<uint64_t> walk_seed_{0x853c49e6748fea9bULL};
 };
 
 // ---------------------------------------------------------------------------
@@ -2416,6 +2551,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              py::call_guard<py::gil_scoped_release>(),
              "num_neg uniform non-neighbour tails per source: (neg, ok); "
              "ok = 0 where max_tries candidates were all rejected")
+        .def("random_walk", &GpuSampler::random_walk, py::arg("start"),
+             py::arg("walk_length"), py::arg("p") = 1.0, py::arg("q") = 1.0,
+             py::arg("max_tries") = 256,
+             py::call_guard<py::gil_scoped_release>(),
+             "uniform (p == q == 1) or node2vec walks: (walk [n, L + 1], "
+             "e_id [n, L] or [n, 0]); -1 after a node with an empty row")
         .def("set_edge_time", &GpuSampler::set_edge_time,
              py::arg("time_csr"),
              "int64 edge times, one per CSR slot, every row ascending")
@@ -2461,6 +2602,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              py::call_guard<py::gil_scoped_release>(),
              "num_neg uniform non-neighbour tails per source: (neg, ok); "
              "ok = 0 where max_tries candidates were all rejected")
+        .def("random_walk", &CpuSampler::random_walk, py::arg("start"),
+             py::arg("walk_length"), py::arg("p") = 1.0, py::arg("q") = 1.0,
+             py::arg("max_tries") = 256, py::arg("want_ids") = false,
+             py::call_guard<py::gil_scoped_release>(),
+             "uniform (p == q == 1) or node2vec walks, every step from its "
+             "exact distribution: (walk [n, L + 1], e_id [n, L] or [n, 0])")
+        .def("set_seed", &CpuSampler::set_seed,
+             "seed of random_walk (the other draws have none)")
         .def("set_edge_time", &CpuSampler::set_edge_time,
              py::arg("time_csr"), py::arg("emit_eid") = false,
              "int64 edge times, one per CSR slot, every row ascending")

@@ -110,6 +110,29 @@ void launch_sample_negative(hipStream_t s, const int64_t* indptr,
                             const uint64_t* rng_dev = nullptr,
                             const int64_t* n_dev = nullptr);
 
+// Random walks: out_walk [n, walk_length + 1], out_walk[i][0] = start[i] and
+// out_walk[i][t + 1] an out-neighbour of out_walk[i][t], -1 from the first
+// node with an empty row on (and after a start outside [0, node_count),
+// which reads no row).  Step 1, and every step when p == q == 1, is uniform
+// over the row's slots; a later step from v, with t the node before it,
+// takes neighbour x in proportion to 1/p if x == t, 1 if x occurs in t's
+// out-row, 1/q otherwise (node2vec).  out_eid (null: no ids) [n,
+// walk_length]: the id of the edge of step t as in launch_sample, -1 where
+// the walk has ended; of several slots of v's row that hold t, the
+// second-order draw may name any.  p == q == 1 runs one lane per walk;
+// anything else one 16-lane subgroup per walk, exact for rows of up to 16
+// slots and by rejection above, max_tries / 16 rounds of 16 tries a step;
+// a step that uses them all takes its last try's slot as drawn.  RNG keyed
+// by (rng_seed (+ *rng_dev), row i, step, try).  One launch, no host sync.
+// Throws unless walk_length >= 1, max_tries >= 16, node_count >= 1 and p, q
+// and their reciprocals are finite and > 0.
+void launch_random_walk(hipStream_t s, const int64_t* indptr,
+                        const int64_t* indices, const int64_t* eid_base,
+                        const int64_t* start, int64_t n, int walk_length,
+                        int64_t node_count, double p, double q, int max_tries,
+                        int64_t* out_walk, int64_t* out_eid,
+                        uint64_t rng_seed, const uint64_t* rng_dev = nullptr);
+
 // Temporal neighbour draw over rows sorted by edge time (ties in original
 // CSR order); time[slot] is one int64 per CSR slot.  A row i is a composite
 // key = root * node_count + v, and an edge of v is eligible iff its time <=

@@ -13,6 +13,8 @@
 //  - Scans use hipCUB (rocPRIM) device scan.
 #include <hipcub/hipcub.hpp>
 
+#include <cmath>
+
 #include "qk_common.h"
 
 namespace qk {
@@ -433,6 +435,301 @@ negative_sample_kernel(const int64_t* __restrict__ indptr,
     }
 }
 
+// ---- random walks -----------------------------------------------------------
+//
+// A walk is a chain of dependent draws, so the parallelism is over walks.
+// Both kernels run all L steps of their walks in one launch and key the
+// stream by the walk's ROW in the batch (not its start node), then by the
+// step: a start node given twice walks independently.  A start outside
+// [0, node_count) is written back as given and walks nowhere (no row is
+// read for it); a walk that reaches an empty row is -1 from there on.
+
+constexpr uint64_t kRowKey = 0x9e3779b97f4a7c15ULL;
+constexpr uint64_t kStepKey = 0x632be59bd9b4e019ULL;
+
+// Uniform in [0, 1) with 53 random bits.  The second-order weights are
+// doubles throughout: 1 / p may be 1e-9 beside a weight of 1, and a 24-bit
+// draw would hit such a return edge once in 2^24 steps instead of never.
+__device__ __forceinline__ double unit_rand(uint64_t h) {
+    return (double)(h >> 11) * 0x1p-53;
+}
+
+// First-order walk: one lane per walk, 64 walks a wave, grid-stride.  A
+// step is two indptr loads, one exact-range draw (mulhi_rand: hub rows are
+// longer than the 2048 that bounded_rand can take) and one indices load,
+// plus the id-map load when ids are asked for.
+//
+// Output: stored directly, not staged in LDS.  Lane i writes its own row
+// of pitch (L + 1) * 8 bytes one entry a step, so a wave's store touches 64
+// lines; but the stores are off the critical path (a step waits for three
+// dependent random loads, nothing waits for a store), consecutive steps of
+// a lane fall into the same line and merge in L2 before they reach HBM,
+// and the whole output is 8 bytes a step against the 3 x 64-byte sectors a
+// step reads.  Staging would need (L + 1) * 8 bytes of LDS per lane, which
+// bounds the walk length by the LDS size or costs a barrier and a flush
+// every few steps, to make coalesced a write that nobody waits for.
+template <bool WITH_EID>
+__global__ void __launch_bounds__(BLOCK)
+uniform_walk_kernel(const int64_t* __restrict__ indptr,
+                    const int64_t* __restrict__ indices,
+                    const int64_t* __restrict__ eid_base,
+                    const int64_t* __restrict__ start, int64_t n, int L,
+                    int64_t node_count, int64_t* __restrict__ out_walk,
+                    int64_t* __restrict__ out_eid, uint64_t rng_seed,
+                    const uint64_t* __restrict__ rng_dev) {
+    if (rng_dev) rng_seed += *rng_dev;
+    int64_t row = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const int64_t row_stride = (int64_t)gridDim.x * BLOCK;
+    for (; row < n; row += row_stride) {
+        int64_t v = start[row];
+        int64_t* walk = out_walk + row * (L + 1);
+        walk[0] = v;
+        if (v < 0 || v >= node_count) v = -1;
+        const uint64_t base = rng_seed + (uint64_t)row * kRowKey;
+        for (int t = 0; t < L; ++t) {
+            int64_t nxt = -1, id = -1;
+            if (v >= 0) {
+                const int64_t beg = indptr[v];
+                const int64_t deg = indptr[v + 1] - beg;
+                if (deg > 0) {
+                    const int64_t at = beg + mulhi_rand(
+                        splitmix64(base + (uint64_t)t * kStepKey),
+                        (uint64_t)deg);
+                    nxt = indices[at];
+                    if (WITH_EID) id = eid_base ? eid_base[at] : at;
+                }
+            }
+            walk[t + 1] = nxt;
+            if (WITH_EID) out_eid[row * L + t] = id;
+            v = nxt;
+        }
+    }
+}
+
+// hit = `cand` occurs in row[0 .. deg), for every lane that has `open` set
+// (the lanes' candidates may differ; a lane that is not open returns
+// false).  The scan of negative_sample_kernel: the row is read once,
+// kNegAhead 16-wide steps a group with the next group requested ahead;
+// each candidate still unhit is handed round by its owner and compared by
+// all lanes with their own neighbours; the scan leaves once every open
+// lane has been hit.  Call it under subgroup-uniform control flow only.
+__device__ __forceinline__ bool subgroup_find(
+    int64_t cand, bool open, const int64_t* __restrict__ row,
+    const int64_t* __restrict__ spare, int64_t deg, int lane,
+    int ballot_shift) {
+    bool hit = false;
+    int64_t now[kNegAhead], next[kNegAhead];
+    load_neighbours(now, row, spare, lane, deg);
+    for (int64_t p0 = 0; p0 < deg; p0 += SUB * kNegAhead) {
+        uint32_t unhit =
+            (uint32_t)(__ballot(open && !hit) >> ballot_shift) & 0xffffu;
+        if (!unhit) break;                                  // uniform
+        load_neighbours(next, row, spare, p0 + SUB * kNegAhead + lane, deg);
+        while (unhit) {                                     // uniform
+            const int owner = __builtin_ctz(unhit);
+            unhit &= unhit - 1;
+            const int64_t c = __shfl(cand, owner, SUB);
+            bool found = false;
+#pragma unroll
+            for (int a = 0; a < kNegAhead; ++a) found |= now[a] == c;
+            const uint32_t any =
+                (uint32_t)(__ballot(found) >> ballot_shift) & 0xffffu;
+            if (any && lane == owner) hit = true;
+        }
+#pragma unroll
+        for (int a = 0; a < kNegAhead; ++a) now[a] = next[a];
+    }
+    return hit;
+}
+
+// How often node x occurs in row[0 .. deg), and the first position where
+// it does (undefined when the count is 0): one full scan, the same
+// loads as subgroup_find.  Subgroup-uniform control flow only.
+__device__ __forceinline__ void subgroup_locate(
+    int64_t x, const int64_t* __restrict__ row,
+    const int64_t* __restrict__ spare, int64_t deg, int lane,
+    int64_t& first, int& count) {
+    int64_t at = INT64_MAX;
+    int cnt = 0;
+    int64_t now[kNegAhead], next[kNegAhead];
+    load_neighbours(now, row, spare, lane, deg);
+    for (int64_t p0 = 0; p0 < deg; p0 += SUB * kNegAhead) {
+        load_neighbours(next, row, spare, p0 + SUB * kNegAhead + lane, deg);
+#pragma unroll
+        for (int a = 0; a < kNegAhead; ++a) {
+            if (now[a] == x) {          // x >= 0, the filler is -1
+                ++cnt;
+                const int64_t p = p0 + a * SUB + lane;
+                at = p < at ? p : at;
+            }
+            now[a] = next[a];
+        }
+    }
+    for (int off = SUB / 2; off > 0; off >>= 1) {
+        cnt += __shfl_xor(cnt, off, SUB);
+        const int64_t o = __shfl_xor(at, off, SUB);
+        at = o < at ? o : at;
+    }
+    first = at;
+    count = cnt;
+}
+
+// Second-order (node2vec) walk: one 16-lane subgroup per walk, four walks a
+// wave.  With t the previous node and v the current one, neighbour x of v
+// weighs inv_p if x == t, 1 if x occurs in t's out-row, inv_q otherwise;
+// the first step, which has no t, is uniform.  Rows are not sorted, so
+// "occurs in t's row" is a scan of that row (subgroup_find), done at most
+// once per round of 16 candidates.
+//
+//  - deg(v) <= 16, exact: lane l holds neighbour l, one scan of t's row
+//    classifies all of them, a subgroup prefix sum of the weights and one
+//    draw against it pick the step.  No rejection: a leaf whose only way
+//    is back to t costs one short scan however large p is.
+//  - deg(v) > 16, rejection, 16 tries a round, lane l owning try l.  The
+//    envelope is M = max(1, inv_q) per slot, plus an appendix of area
+//    max(0, inv_p - M) per occurrence of t in v's row (counted once per
+//    step, and only when inv_p > M) that is accepted outright as the
+//    return edge.  A slot try draws a height u in [0, M): it is settled
+//    without the class when the candidate is t (accept iff u < inv_p) or
+//    when u < min(1, inv_q), a weight every other neighbour reaches.  The
+//    tries left open, and numbered below the first accepted one, are tested
+//    against t's row in one scan.  The lowest-numbered accepted try is the
+//    step: exactly sequential rejection sampling.  Rounds are counted,
+//    `rounds` of them (max_tries / 16, from the host); a step that uses
+//    them all up takes the slot of its last try as drawn.
+//
+// Stream key: (walk row, step), then the try number.  v, t and everything
+// derived from them are uniform across the subgroup, and so is every
+// branch around a shuffle or ballot.  Lane 0 stores the output, directly
+// (see uniform_walk_kernel: 4 walks a wave make coalescing moot).
+template <bool WITH_EID>
+__global__ void __launch_bounds__(BLOCK)
+node2vec_walk_kernel(const int64_t* __restrict__ indptr,
+                     const int64_t* __restrict__ indices,
+                     const int64_t* __restrict__ eid_base,
+                     const int64_t* __restrict__ start, int64_t n, int L,
+                     int64_t node_count, double inv_p, double inv_q,
+                     int rounds, int64_t* __restrict__ out_walk,
+                     int64_t* __restrict__ out_eid, uint64_t rng_seed,
+                     const uint64_t* __restrict__ rng_dev) {
+    if (rng_dev) rng_seed += *rng_dev;
+    const int sub_id = threadIdx.x / SUB;
+    const int lane = threadIdx.x % SUB;
+    // this subgroup's 16 bits of the wave's 64-bit ballot
+    const int ballot_shift = (threadIdx.x % kWaveSize) - lane;
+    const double envelope = inv_q > 1.0 ? inv_q : 1.0;      // M
+    const double sure = inv_q < 1.0 ? inv_q : 1.0;
+    const double extra = inv_p > envelope ? inv_p - envelope : 0.0;
+    int64_t row = (int64_t)blockIdx.x * ROWS_PER_BLOCK + sub_id;
+    const int64_t row_stride = (int64_t)gridDim.x * ROWS_PER_BLOCK;
+
+    for (; row < n; row += row_stride) {
+        int64_t v = start[row];
+        if (lane == 0) out_walk[row * (L + 1)] = v;
+        if (v < 0 || v >= node_count) v = -1;
+        // the previous node and its row, kept from the step before
+        int64_t prev = -1, prev_beg = 0, prev_deg = 0;
+        const uint64_t base = rng_seed + (uint64_t)row * kRowKey;
+        for (int t = 0; t < L; ++t) {
+            int64_t beg = 0, deg = 0;
+            if (v >= 0) {
+                beg = indptr[v];
+                deg = indptr[v + 1] - beg;
+            }
+            int64_t at = -1, nxt = -1;      // drawn row position, its node
+            const uint64_t key = splitmix64(base + (uint64_t)t * kStepKey);
+            const int64_t* vrow = indices + beg;
+            const int64_t* prow = indices + prev_beg;
+            if (deg > 0 && prev < 0) {
+                // first step: uniform, every lane the same draw and load
+                at = mulhi_rand(splitmix64(key), (uint64_t)deg);
+                nxt = vrow[at];
+            } else if (deg > 0 && deg <= SUB) {
+                const bool held = lane < deg;
+                const int64_t x = *(held ? vrow + lane : indptr);
+                const bool is_ret = held && x == prev;
+                // q == 1: both other classes weigh 1, no scan
+                const bool hit = subgroup_find(
+                    x, held && !is_ret && inv_q != 1.0, prow, indptr,
+                    prev_deg, lane, ballot_shift);
+                double cum = !held ? 0.0 : is_ret ? inv_p
+                                         : hit    ? 1.0
+                                                  : inv_q;
+                for (int off = 1; off < SUB; off <<= 1) {
+                    const double o = __shfl_up(cum, off, SUB);
+                    if (lane >= off) cum += o;
+                }
+                const double total = __shfl(cum, SUB - 1, SUB);
+                const double u = unit_rand(splitmix64(key)) * total;
+                // u == total can only come from rounding: the last one
+                const uint32_t over =
+                    (uint32_t)(__ballot(held && cum > u) >> ballot_shift) &
+                    0xffffu;
+                at = over ? __builtin_ctz(over) : deg - 1;
+                nxt = __shfl(x, (int)at, SUB);
+            } else if (deg > 0) {
+                int64_t ret_at = 0;
+                int ret_count = 0;
+                if (extra > 0.0)                            // uniform
+                    subgroup_locate(prev, vrow, indptr, deg, lane, ret_at,
+                                    ret_count);
+                const double appendix = ret_count * extra;
+                const double area = (double)deg * envelope + appendix;
+                for (int r = 0; r < rounds; ++r) {
+                    const uint64_t h1 = splitmix64(
+                        key + (uint64_t)(r * SUB + lane + 1) * kRowKey);
+                    const uint64_t h2 = splitmix64(h1);
+                    const uint64_t h3 = splitmix64(h2);
+                    // appendix == 0 never passes this test
+                    const bool app = unit_rand(h1) * area < appendix;
+                    const int64_t slot =
+                        app ? ret_at : mulhi_rand(h2, (uint64_t)deg);
+                    const int64_t loaded = *(app ? indptr : vrow + slot);
+                    const int64_t x = app ? prev : loaded;
+                    const double u = unit_rand(h3) * envelope;
+                    const bool is_ret = x == prev;
+                    bool acc = app || u < (is_ret ? inv_p : sure);
+                    // the class decides; but no try after the first
+                    // accepted one can be the step
+                    bool open = !acc && !is_ret;
+                    uint32_t accb =
+                        (uint32_t)(__ballot(acc) >> ballot_shift) & 0xffffu;
+                    if (accb) open = open && lane < __builtin_ctz(accb);
+                    const uint32_t any_open =
+                        (uint32_t)(__ballot(open) >> ballot_shift) & 0xffffu;
+                    if (any_open) {                         // uniform
+                        const bool hit = subgroup_find(
+                            x, open, prow, indptr, prev_deg, lane,
+                            ballot_shift);
+                        // u in [inv_q, 1): only an adjacent x (weight 1)
+                        // is above it; u in [1, inv_q): only a far one
+                        if (open) acc = inv_q < 1.0 ? hit : !hit;
+                        accb = (uint32_t)(__ballot(acc) >> ballot_shift) &
+                               0xffffu;
+                    }
+                    // nothing accepted: the last try stands until a later
+                    // round accepts one
+                    const int win = accb ? __builtin_ctz(accb) : SUB - 1;
+                    at = __shfl(slot, win, SUB);
+                    nxt = __shfl(x, win, SUB);
+                    if (accb) break;                        // uniform
+                }
+            }
+            if (lane == 0) {
+                out_walk[row * (L + 1) + t + 1] = nxt;
+                if (WITH_EID)
+                    out_eid[row * L + t] =
+                        nxt < 0 ? -1
+                                : eid_base ? eid_base[beg + at] : beg + at;
+            }
+            prev = v;
+            prev_beg = beg;
+            prev_deg = deg;
+            v = nxt;
+        }
+    }
+}
+
 // ---- temporal draw ----------------------------------------------------------
 //
 // Rows are sorted by edge time (ties in original CSR order), so the edges of
@@ -708,6 +1005,40 @@ void launch_sample_negative(hipStream_t s, const int64_t* indptr,
     negative_sample_kernel<<<grid_for(n, ROWS_PER_BLOCK), BLOCK, 0, s>>>(
         indptr, indices, src, n, num_neg, node_count, max_tries, out_neg,
         out_ok, rng_seed, rng_dev, n_dev);
+    QK_CHECK_HIP(hipGetLastError());
+}
+
+void launch_random_walk(hipStream_t s, const int64_t* indptr,
+                        const int64_t* indices, const int64_t* eid_base,
+                        const int64_t* start, int64_t n, int walk_length,
+                        int64_t node_count, double p, double q, int max_tries,
+                        int64_t* out_walk, int64_t* out_eid,
+                        uint64_t rng_seed, const uint64_t* rng_dev) {
+    if (walk_length < 1)
+        throw std::runtime_error("random_walk: walk_length must be >= 1");
+    if (!(p > 0) || !(q > 0) || !std::isfinite(p) || !std::isfinite(q) ||
+        !std::isfinite(1.0 / p) || !std::isfinite(1.0 / q))
+        throw std::runtime_error(
+            "random_walk: p and q must be finite and > 0");
+    if (max_tries < SUB)
+        throw std::runtime_error("random_walk: max_tries must be >= 16");
+    if (node_count < 1)
+        throw std::runtime_error("random_walk: the graph has no nodes");
+    if (n == 0) return;
+    if (p == 1.0 && q == 1.0) {
+        auto kern = out_eid ? uniform_walk_kernel<true>
+                            : uniform_walk_kernel<false>;
+        kern<<<grid_for(n, BLOCK), BLOCK, 0, s>>>(
+            indptr, indices, eid_base, start, n, walk_length, node_count,
+            out_walk, out_eid, rng_seed, rng_dev);
+    } else {
+        auto kern = out_eid ? node2vec_walk_kernel<true>
+                            : node2vec_walk_kernel<false>;
+        kern<<<grid_for(n, ROWS_PER_BLOCK), BLOCK, 0, s>>>(
+            indptr, indices, eid_base, start, n, walk_length, node_count,
+            1.0 / p, 1.0 / q, max_tries / SUB, out_walk, out_eid, rng_seed,
+            rng_dev);
+    }
     QK_CHECK_HIP(hipGetLastError());
 }
 

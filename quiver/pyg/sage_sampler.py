@@ -403,6 +403,75 @@ class GraphSageSampler:
         src = src.to(self.device).contiguous()
         return self.quiver.sample_negative(src, int(num_neg), int(neg_tries))
 
+    def random_walk(self, start, walk_length, p=1.0, q=1.0, max_tries=256):
+        """Random walks of `walk_length` steps, one from every entry of
+        `start`: uniform for p == q == 1 (DeepWalk), else node2vec's
+        second-order walk.
+
+        Args:
+            start: int64 [B] node ids, a tensor (CPU or GPU) or a list.  A
+                node given several times starts as many independent walks.
+            walk_length: steps per walk, >= 1.
+            p, q: node2vec's return and in-out parameters, finite and > 0.
+                The first step is uniform over the start's row, an edge
+                that occurs several times counting each time.  A later
+                step from v, with t the node before it, takes neighbour x
+                of v with probability proportional to 1/p if x == t (also
+                when t has a self-loop), 1 if x occurs in the out-row of
+                t, 1/q otherwise.
+            max_tries: >= 16.  GPU and UVA mode draw a step out of a row
+                longer than 16 by rejection, 16 candidates a round and
+                max_tries // 16 rounds at most; a step that uses them all
+                up takes its last candidate whatever its weight.  A
+                candidate other than the return edge is accepted with
+                probability at least min(q, 1/q), so with f the share of
+                the row's slots that hold t, a step is exhausted with
+                probability at most (1 - (1 - f) * min(q, 1/q)) **
+                max_tries: under 1e-4 at the default for q in [1/20, 20]
+                and f <= 1/4, and it takes a row made almost wholly of
+                copies of the return edge together with a large p, or an
+                extreme q, to see it.  Rows of at most 16 edges, and CPU
+                mode throughout, draw from the exact distribution and
+                ignore max_tries.
+
+        Returns (walk, e_id) on the sampler's device.  `walk` is int64
+        [B, walk_length + 1]: walk[:, 0] == start, and walk[i, t + 1] is an
+        out-neighbour of walk[i, t].  A walk that reaches a node without
+        out-edges stops there: every later entry is -1.  `e_id` is int64
+        [B, walk_length] on a sampler built with return_eid=True, the id
+        (as in `Adj.e_id`) of the edge from walk[i, t] to walk[i, t + 1]
+        and -1 where walk[i, t + 1] is; else it is empty, [B, 0].
+
+        There is no edge-weighted and no temporal walk: a sampler built
+        with `edge_weight` raises, one built with `edge_time` walks the
+        whole graph whatever the times.  Start ids are range-checked on a
+        CPU input only; an id outside the graph on a GPU input yields the
+        row [id, -1, -1, ...].
+        """
+        if self.w_csr_ is not None:
+            raise ValueError("random_walk on a sampler built with "
+                             "edge_weight: there is no weighted walk")
+        if not all(x > 0 and x != float("inf") for x in (p, q)):
+            raise ValueError(f"p and q must be finite and > 0, got {p}, {q}")
+        if walk_length < 1:
+            raise ValueError(f"walk_length must be >= 1, got {walk_length}")
+        if max_tries < 16:
+            raise ValueError(f"max_tries must be >= 16, got {max_tries}")
+        self.lazy_init_quiver()
+        if not isinstance(start, torch.Tensor):
+            start = torch.tensor(start, dtype=torch.long)
+        self._check_ids(start, "start", (None,))
+        start = start.to(self.device).contiguous()
+        length = int(walk_length)
+        if start.numel() == 0:
+            return (start.new_empty((0, length + 1)),
+                    start.new_empty((0, length if self.return_eid else 0)))
+        args = (start, length, float(p), float(q), int(max_tries))
+        with trace_scope("sampler.random_walk"):
+            if self.mode == "CPU":
+                return self.quiver.random_walk(*args, self.return_eid)
+            return self.quiver.random_walk(*args)
+
     def sample_links(self, edge_label_index, num_neg=1, neg_tries=16,
                      edge_label_time=None):
         """One link-prediction batch: the positive edges given, `num_neg`
