@@ -284,6 +284,110 @@ def bench_walk(mode, shape, topo, p, q, length=20, batches=(1024, 65536),
     return res
 
 
+class TorchSubgraph:
+    """The comparison for GraphSageSampler.subgraph in GPU mode: the same
+    (n_id, edge_index) from torch ops alone on device-resident indptr /
+    indices.  Rows are expanded with repeat_interleave and membership and
+    local ids come from one dense lookup tensor over all nodes, kept
+    between calls and reset after each."""
+
+    def __init__(self, indptr, indices):
+        self.indptr, self.indices = indptr, indices
+        self.lookup = torch.full((indptr.numel() - 1,), -1,
+                                 dtype=torch.long, device=indptr.device)
+
+    def __call__(self, nodes):
+        dev = nodes.device
+        uniq, inv = torch.unique(nodes, return_inverse=True)
+        first = torch.full_like(uniq, nodes.numel()).scatter_reduce_(
+            0, inv, torch.arange(nodes.numel(), device=dev), "amin")
+        n_id = uniq[torch.argsort(first)]
+        n = n_id.numel()
+        self.lookup[n_id] = torch.arange(n, device=dev)
+        beg = self.indptr[n_id]
+        deg = self.indptr[n_id + 1] - beg
+        row = torch.repeat_interleave(torch.arange(n, device=dev), deg)
+        start = torch.cumsum(deg, 0) - deg
+        slot = torch.arange(row.numel(), device=dev) + (beg - start)[row]
+        src = self.lookup[self.indices[slot]]
+        keep = src >= 0
+        edge_index = torch.stack([src[keep], row[keep]])
+        self.lookup[n_id] = -1
+        return n_id, edge_index
+
+
+def bench_subgraph(mode, shape, topo, iters=10, repeats=7, warmup=2,
+                   device=0, chunks=(64, 256, 1024), passes=10):
+    """subgraph on three kinds of node set: the nodes of a GraphSAINT
+    random-walk batch (3000 roots, walks of 2 steps), 100 000 uniform
+    random nodes, and, for the cost of a hub row, 1024 uniform nodes with
+    and without node 0 (the graph's longest row).  Timed per set: the
+    engine at every built chunk size, the public call, sample_saint_rw as
+    a whole (walk + subgraph) and, in GPU mode, TorchSubgraph.  Each repeat
+    times `passes` rounds over `iters` different sets for each in turn;
+    reported are the median and the min..max over the repeats in ms per
+    call, the mean slots of the sets' rows and edges found, and for UVA
+    mode the host bytes the two passes read (16 B a slot)."""
+    cfg = SHAPES[shape]
+    sampler = quiver.GraphSageSampler(topo, cfg["fanout"], device=device,
+                                      mode=mode)
+    sampler.lazy_init_quiver()
+    dev = f"cuda:{device}"
+    sync = torch.cuda.synchronize
+    g = torch.Generator().manual_seed(7)
+    n_nodes = cfg["nodes"]
+    roots = [torch.randint(0, cfg["train"], (3000,), generator=g).to(dev)
+             for _ in range(iters)]
+
+    def walk_nodes(r):
+        walk = sampler.random_walk(r, 2)[0]
+        return torch.where(walk < 0, walk[:, :1], walk).t().reshape(-1)
+
+    no_hub = [1 + torch.randint(0, n_nodes - 1, (1024,), generator=g)
+              .to(dev) for _ in range(iters)]
+    sets = dict(
+        saint_rw=[walk_nodes(r) for r in roots],
+        uniform_100k=[torch.randint(0, n_nodes, (100_000,), generator=g)
+                      .to(dev) for _ in range(iters)],
+        no_hub_1k=no_hub,
+        hub_1k=[torch.cat([s.new_zeros(1), s]) for s in no_hub])
+    res = dict(mode=mode, shape=shape, subgraph=True, iters=iters,
+               passes=passes, repeats=repeats, default_chunk=quiver._ext.subgraph_chunk_slots(),
+               sets={})
+    if mode == "GPU":
+        torch_sub = TorchSubgraph(topo.indptr.to(dev), topo.indices.to(dev))
+    degree = topo.degree.to(dev)
+    for name, node_sets in sets.items():
+        parts = {f"chunk_{c}": (lambda s, c=c: sampler.quiver.subgraph(s, c))
+                 for c in chunks}
+        parts["subgraph"] = sampler.subgraph
+        if mode == "GPU":
+            parts["torch"] = torch_sub
+        lists = {k: node_sets for k in parts}
+        if name == "saint_rw":
+            parts["sample_saint_rw"] = lambda r: sampler.sample_saint_rw(r, 2)
+            lists["sample_saint_rw"] = roots
+        for k, fn in parts.items():
+            _timed(fn, lists[k][:warmup], sync)
+        ms = {k: [] for k in parts}
+        for _ in range(repeats):
+            for k, fn in parts.items():
+                ms[k].append(_timed(fn, lists[k] * passes, sync))
+        subs = [sampler.subgraph(s) for s in node_sets]
+        slots = float(np.mean([int(degree[b.n_id].sum()) for b in subs]))
+        cell = {k + "_ms": _stats(v) for k, v in ms.items()}
+        cell.update(
+            nodes=float(np.mean([b.n_id.numel() for b in subs])),
+            row_slots=slots,
+            edges=float(np.mean([b.edge_index.size(1) for b in subs])))
+        if mode == "UVA":
+            cell["host_bytes_read"] = 16 * slots
+            cell["host_gbps"] = 16 * slots / (
+                cell["subgraph_ms"]["median"] * 1e-3) / 1e9
+        res["sets"][name] = cell
+    return res
+
+
 if __name__ == "__main__":
     p = argparse.ArgumentParser()
     p.add_argument("--modes", default="UVA,GPU,CPU")
@@ -315,7 +419,25 @@ if __name__ == "__main__":
     p.add_argument("--p", type=float, default=0.5)
     p.add_argument("--q", type=float, default=2.0)
     p.add_argument("--walk-length", type=int, default=20)
+    p.add_argument("--subgraph", action="store_true",
+                   help="time subgraph (GraphSAINT random-walk sets, 100 000 "
+                        "uniform nodes, a set with and without the hub row; "
+                        "chunks of 64, 256 and 1024 slots) in GPU and UVA "
+                        "mode, beside a plain-torch version in GPU mode")
     args = p.parse_args()
+    if args.subgraph:
+        assert torch.cuda.is_available(), "--subgraph needs a GPU"
+        for shape in args.shapes.split(","):
+            cfg = SHAPES[shape]
+            indptr, indices = make_graph(cfg["nodes"], cfg["edges"])
+            topo = quiver.CSRTopo(indptr=indptr, indices=indices)
+            for mode in args.modes.split(","):
+                if mode == "CPU":       # timed on the GPU only
+                    continue
+                print(json.dumps(bench_subgraph(
+                    mode, shape, topo, iters=min(args.iters, 10),
+                    repeats=args.repeats)), flush=True)
+        sys.exit(0)
     if args.walk:
         assert torch.cuda.is_available(), "--walk needs a GPU"
         for shape in args.shapes.split(","):

@@ -314,6 +314,96 @@ class GpuSampler {
         return {walk, ids};
     }
 
+    // Induced subgraph of `nodes` (duplicates allowed): (n_id, edges,
+    // dst_ptr), contract at launch_subgraph_fill.  n_id [n] holds the
+    // distinct nodes in first-occurrence order, edges is [2, m] (local src,
+    // local dst), or [3, m] with the edge ids when they are emitted, and
+    // dst_ptr [n + 1] the segment pointer of edges[1].  Nothing is drawn.
+    // One host sync: a single device-to-host copy of {n, m, ids outside
+    // the graph}; everything before it is sized by host bounds and reads
+    // exact counts on the device.  An id outside [0, node_count) raises
+    // ValueError after that copy.  `chunk_slots` (0: the default) is for
+    // tuning only.
+    std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> subgraph(
+        torch::Tensor nodes, int chunk_slots) {
+        DeviceScope g(device_);
+        auto stream = current_stream();
+        TORCH_CHECK(nodes.dtype() == torch::kInt64, "nodes must be int64");
+        TORCH_CHECK(nodes.device().is_cuda() &&
+                        nodes.device().index() == device_,
+                    "nodes must be on the sampler's GPU");
+        TORCH_CHECK(nodes.dim() == 1 && nodes.is_contiguous(),
+                    "nodes must be a contiguous 1-D tensor");
+        const int chunk =
+            chunk_slots > 0 ? chunk_slots : qk::subgraph_chunk_slots();
+        const int64_t B = nodes.numel();
+        // the node table keeps first positions as int32
+        TORCH_CHECK(B < INT32_MAX, "subgraph: too many nodes");
+        auto opts = nodes.options();
+        const int64_t rows = emit_eid_ ? 3 : 2;
+        if (B == 0)
+            return {torch::empty({0}, opts), torch::empty({rows, 0}, opts),
+                    torch::zeros({1}, opts)};
+        if (node_count_ == 0)
+            throw py::value_error("subgraph: the graph has no nodes");
+
+        // {n, m, bad ids, chunks}: the first three go to the host together
+        auto sizes = torch::zeros({4}, opts);
+        int64_t* sd = sizes.data_ptr<int64_t>();
+        const int64_t *n_dev = sd, *chunks_dev = sd + 3;
+
+        // 1. node set: the reindex chain over ids known to be in range
+        auto clean = torch::empty({B}, opts);
+        qk::launch_subgraph_check_ids(stream, nodes.data_ptr<int64_t>(), B,
+                                      node_count_, clean.data_ptr<int64_t>(),
+                                      sd + 2);
+        auto table = reindex_build(stream, clean.data_ptr<int64_t>(), B,
+                                   nullptr, 0, nullptr, nullptr, sd, opts);
+        auto n_id = torch::empty({B}, opts);
+        qk::launch_compact_unique(stream, table.set,
+                                  table.scanned.data_ptr<int64_t>(),
+                                  table.flags.data_ptr<int64_t>(),
+                                  n_id.data_ptr<int64_t>());
+
+        // 2. membership bitmap and the chunks of every row
+        auto bitmap = torch::zeros({(node_count_ + 63) / 64}, opts);
+        auto row_chunks = torch::empty({B + 1}, opts);
+        qk::launch_subgraph_mark(stream, indptr_.data_ptr<int64_t>(),
+                                 n_id.data_ptr<int64_t>(), B, n_dev,
+                                 node_count_, chunk,
+                                 bitmap.data_ptr<int64_t>(),
+                                 row_chunks.data_ptr<int64_t>());
+        auto row_first = exclusive_scan(row_chunks, sd + 3, stream);
+
+        // 3. count per chunk, scan, the one sync, fill
+        qk::SubgraphSet set = {indptr_.data_ptr<int64_t>(), indices_dptr_,
+                               node_count_, n_id.data_ptr<int64_t>(),
+                               row_first.data_ptr<int64_t>(), B, n_dev,
+                               chunks_dev, B + indices_.numel() / chunk,
+                               bitmap.data_ptr<int64_t>(), chunk};
+        auto chunk_count = torch::empty({set.chunk_ub + 1}, opts);
+        qk::launch_subgraph_count(stream, set,
+                                  chunk_count.data_ptr<int64_t>());
+        auto chunk_off = exclusive_scan(chunk_count, sd + 1, stream);
+        auto sizes_host = sizes.narrow(0, 0, 3).cpu();
+        const int64_t* sh = sizes_host.data_ptr<int64_t>();
+        const int64_t n = sh[0], m = sh[1];
+        if (sh[2] > 0)
+            throw py::value_error(
+                "subgraph: " + std::to_string(sh[2]) + " of the " +
+                std::to_string(B) + " nodes lie outside [0, " +
+                std::to_string(node_count_) + ")");
+        auto edges = torch::empty({rows, m}, opts);
+        auto dst_ptr = torch::empty({n + 1}, opts);
+        int64_t* ep = edges.data_ptr<int64_t>();
+        qk::launch_subgraph_fill(stream, set, eid_dptr_,
+                                 chunk_off.data_ptr<int64_t>(), table.set, n,
+                                 m, ep, ep + m,
+                                 emit_eid_ ? ep + 2 * m : nullptr,
+                                 dst_ptr.data_ptr<int64_t>());
+        return {n_id.narrow(0, 0, n), edges, dst_ptr};
+    }
+
     // Opt-in edge times for sample_neighbor_temporal: one int64 per CSR
     // slot, every row ascending (the caller built the engine from rows
     // sorted by time); placed like `indices`.
@@ -1058,6 +1148,66 @@ class CpuSampler {
             }
         });
         return {walk, ids};
+    }
+
+    // Induced subgraph of `nodes`, the contract and output order of
+    // GpuSampler::subgraph: (n_id, edges [2 or 3, m], dst_ptr [n + 1]).  A
+    // count pass and a fill pass over the set's rows, membership and local
+    // ids from one hash map.
+    std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> subgraph(
+        torch::Tensor nodes, bool want_ids) {
+        TORCH_CHECK(nodes.dtype() == torch::kInt64, "nodes must be int64");
+        TORCH_CHECK(nodes.device().is_cpu(), "nodes must be a CPU tensor");
+        TORCH_CHECK(nodes.dim() == 1 && nodes.is_contiguous(),
+                    "nodes must be a contiguous 1-D tensor");
+        const int64_t B = nodes.numel();
+        const int64_t* np = nodes.data_ptr<int64_t>();
+        const int64_t* indptr = indptr_.data_ptr<int64_t>();
+        const int64_t* indices = indices_.data_ptr<int64_t>();
+        const int64_t* eid = eid_.defined() ? eid_.data_ptr<int64_t>()
+                                            : nullptr;
+        std::unordered_map<int64_t, int64_t> local;
+        local.reserve(2 * B);
+        std::vector<int64_t> set;
+        for (int64_t i = 0; i < B; ++i) {
+            if (np[i] < 0 || np[i] >= node_count_)
+                throw py::value_error(
+                    "subgraph: node " + std::to_string(np[i]) +
+                    " lies outside [0, " + std::to_string(node_count_) + ")");
+            if (local.emplace(np[i], (int64_t)set.size()).second)
+                set.push_back(np[i]);
+        }
+        const int64_t n = set.size();
+        auto dst_ptr = torch::zeros({n + 1}, nodes.options());
+        int64_t* dp = dst_ptr.data_ptr<int64_t>();
+        at::parallel_for(0, n, 64, [&](int64_t b, int64_t e) {
+            for (int64_t i = b; i < e; ++i) {
+                int64_t hits = 0;
+                for (int64_t s = indptr[set[i]]; s < indptr[set[i] + 1]; ++s)
+                    hits += local.count(indices[s]);
+                dp[i + 1] = hits;
+            }
+        });
+        for (int64_t i = 0; i < n; ++i) dp[i + 1] += dp[i];
+        const int64_t m = dp[n];
+        auto edges = torch::empty({want_ids ? 3 : 2, m}, nodes.options());
+        int64_t* ep = edges.data_ptr<int64_t>();
+        at::parallel_for(0, n, 64, [&](int64_t b, int64_t e) {
+            for (int64_t i = b; i < e; ++i) {
+                int64_t at = dp[i];
+                for (int64_t s = indptr[set[i]]; s < indptr[set[i] + 1]; ++s) {
+                    auto it = local.find(indices[s]);
+                    if (it == local.end()) continue;
+                    ep[at] = it->second;
+                    ep[m + at] = i;
+                    if (want_ids) ep[2 * m + at] = eid ? eid[s] : s;
+                    ++at;
+                }
+            }
+        });
+        auto n_id = torch::empty({n}, nodes.options());
+        std::copy(set.begin(), set.end(), n_id.data_ptr<int64_t>());
+        return {n_id, edges, dst_ptr};
     }
 
     std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> reindex_single(
@@ -2557,6 +2707,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              py::call_guard<py::gil_scoped_release>(),
              "uniform (p == q == 1) or node2vec walks: (walk [n, L + 1], "
              "e_id [n, L] or [n, 0]); -1 after a node with an empty row")
+        .def("subgraph", &GpuSampler::subgraph, py::arg("nodes"),
+             py::arg("chunk_slots") = 0,
+             py::call_guard<py::gil_scoped_release>(),
+             "induced subgraph of a node set, one sync: (n_id, edges [2 or "
+             "3, m], dst_ptr [n + 1]); ValueError on an id outside the graph")
         .def("set_edge_time", &GpuSampler::set_edge_time,
              py::arg("time_csr"),
              "int64 edge times, one per CSR slot, every row ascending")
@@ -2608,6 +2763,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              py::call_guard<py::gil_scoped_release>(),
              "uniform (p == q == 1) or node2vec walks, every step from its "
              "exact distribution: (walk [n, L + 1], e_id [n, L] or [n, 0])")
+        .def("subgraph", &CpuSampler::subgraph, py::arg("nodes"),
+             py::arg("want_ids") = false,
+             py::call_guard<py::gil_scoped_release>(),
+             "induced subgraph of a node set: (n_id, edges [2 or 3, m], "
+             "dst_ptr [n + 1]); ValueError on an id outside the graph")
         .def("set_seed", &CpuSampler::set_seed,
              "seed of random_walk (the other draws have none)")
         .def("set_edge_time", &CpuSampler::set_edge_time,
@@ -2688,6 +2848,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("segment_mean_lanes", &qk::segment_mean_lanes, py::arg("dim"),
           py::arg("bf16") = false);
     m.def("segment_mean_rows_in_flight", &qk::segment_mean_rows_in_flight);
+    m.def("subgraph_chunk_slots", &qk::subgraph_chunk_slots,
+          "CSR slots per unit of work of the subgraph kernels");
 
     m.def("tall_gemm", &tall_gemm,
           "C[M,N] = A[M,K] @ B[K,N] (+bias), M huge, MFMA 32x32 tiles");

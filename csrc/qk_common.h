@@ -9,6 +9,7 @@
 // Kernel files, in the order of the sections below:
 //   sample_kernels.hip   neighbour sampling, scans, access probabilities
 //   reindex_kernels.hip  hash-table frontier reindex
+//   subgraph_kernels.hip induced subgraph of a node set
 //   gather_kernels.hip   sharded feature gather / scatter
 //   gemm_kernels.hip     tall-M GEMM
 //   wgrad_kernels.hip    tall-skinny split-K weight gradient
@@ -199,6 +200,60 @@ void launch_lookup_local(hipStream_t s, const ReindexSet& w, int64_t* col_idx);
 void launch_expand_rows(hipStream_t s, const int64_t* prefix,
                         const int64_t* counts, int64_t n_seeds,
                         int64_t* row_idx, const int64_t* n_dev = nullptr);
+
+// ---------- induced subgraph (subgraph_kernels.hip) ----------
+//
+// The edges between the nodes of a set: one output column per CSR slot s of
+// a set row u whose indices[s] is in the set too, rows in the set's local
+// id order, slots in CSR order.  The caller builds the set's node table
+// with the reindex chain above (local ids filled by launch_compact_unique)
+// and runs, on one stream: check_ids, the chain, mark, a scan of
+// row_chunks, count, a scan of chunk_count, one sync for the sizes, fill.
+// A chunk is up to `chunk` consecutive slots of one row and the unit of
+// work of count and fill.
+
+// slots per chunk the engine uses; 64, 256 and 1024 are built
+int subgraph_chunk_slots();
+
+// clean[i] = nodes[i], or 0 where it lies outside [0, node_count); *bad
+// (pre-zeroed) += the number of such ids.
+void launch_subgraph_check_ids(hipStream_t s, const int64_t* nodes, int64_t n,
+                               int64_t node_count, int64_t* clean,
+                               int64_t* bad);
+// Sets the bit of every n_id[i], i < *n_dev, in bitmap (int64
+// [ceil(node_count / 64)], pre-zeroed) and writes row_chunks[i] =
+// ceil(degree / chunk); entries [*n_dev, n] are 0 (n + 1 entries in all).
+void launch_subgraph_mark(hipStream_t s, const int64_t* indptr,
+                          const int64_t* n_id, int64_t n,
+                          const int64_t* n_dev, int64_t node_count, int chunk,
+                          int64_t* bitmap, int64_t* row_chunks);
+struct SubgraphSet {
+    const int64_t* indptr;
+    const int64_t* indices;
+    int64_t node_count;
+    const int64_t* n_id;        // distinct ids in local id order
+    const int64_t* row_first;   // [n + 1] exclusive scan of row_chunks
+    int64_t n;                  // host bound of the set's size
+    const int64_t* n_dev;       // its exact size (device)
+    const int64_t* chunks_dev;  // sum of row_chunks (device)
+    int64_t chunk_ub;           // host bound of it: n + slots / chunk
+    const int64_t* bitmap;
+    int chunk;
+};
+// chunk_count[c] = set members among chunk c's slots; entries
+// [*chunks_dev, chunk_ub] are 0 (chunk_ub + 1 entries in all).
+void launch_subgraph_count(hipStream_t s, const SubgraphSet& g,
+                           int64_t* chunk_count);
+// chunk_off: exclusive scan of chunk_count; n, m: the exact set size and
+// edge total, read back by the caller.  Writes out_src[m] (local id of the
+// neighbour, from `table`), out_dst[m] (local id of the row), out_id[m]
+// unless null (eid_base[slot], or the slot when eid_base is null) and
+// dst_ptr[n + 1], the first column of every row with dst_ptr[n] = m.
+void launch_subgraph_fill(hipStream_t s, const SubgraphSet& g,
+                          const int64_t* eid_base, const int64_t* chunk_off,
+                          const ReindexSet& table, int64_t n, int64_t m,
+                          int64_t* out_src, int64_t* out_dst, int64_t* out_id,
+                          int64_t* dst_ptr);
 
 // ---------- feature gather (gather_kernels.hip) ----------
 

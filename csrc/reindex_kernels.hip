@@ -9,6 +9,7 @@
 //    always get ids [0, n_seeds) in order.
 //  - plain grid-stride wave64 kernels; device-scope atomics (cross-XCD safe).
 #include "qk_common.h"
+#include "hash_probe.h"
 
 namespace qk {
 
@@ -16,28 +17,6 @@ namespace {
 
 constexpr int BLOCK = 256;
 constexpr int32_t POS_EMPTY = INT32_MAX;
-
-__device__ __forceinline__ uint64_t hash64(uint64_t x) {
-    x ^= x >> 33;
-    x *= 0xff51afd7ed558ccdULL;
-    x ^= x >> 33;
-    x *= 0xc4ceb9fe1a85ec53ULL;
-    x ^= x >> 33;
-    return x;
-}
-
-__device__ __forceinline__ int64_t probe_find(const int64_t* keys,
-                                              int64_t capacity, int64_t key) {
-    int64_t mask = capacity - 1;
-    int64_t slot = (int64_t)(hash64((uint64_t)key) & (uint64_t)mask);
-    while (true) {
-        int64_t k = keys[slot];
-        if (k == key) return slot;
-        // key must be present when called after insert; -1 means corrupt use
-        if (k == -1) return -1;
-        slot = (slot + 1) & mask;
-    }
-}
 
 __device__ __forceinline__ const int64_t* combined_at(
     const int64_t* seeds, int64_t n_seeds, const int64_t* nbrs, int64_t i,

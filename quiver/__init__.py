@@ -7,7 +7,7 @@ collectives, zero-copy pinned-host tiers.
 """
 from .feature import Feature, DistFeature, PartitionInfo, DeviceConfig
 from .pyg import (GraphSageSampler, MixedGraphSageSampler, SampleJob,
-                  LinkBatch, TemporalBatch)
+                  LinkBatch, TemporalBatch, SubgraphBatch)
 from .utils import CSRTopo
 from .utils import Topo as p2pCliqueTopo
 from .utils import init_p2p
@@ -27,7 +27,7 @@ __version__ = "0.1.0"
 __all__ = [
     "Feature", "DistFeature", "PartitionInfo", "DeviceConfig", "CSRTopo",
     "GraphSageSampler", "MixedGraphSageSampler", "SampleJob", "LinkBatch",
-    "TemporalBatch",
+    "TemporalBatch", "SubgraphBatch",
     "quiver_partition_feature", "load_quiver_feature_partition",
     "p2pCliqueTopo", "init_p2p", "getNcclId", "NcclComm",
     "RequestBatcher", "HybridSampler", "InferenceServer",

@@ -1,5 +1,6 @@
 from .sage_sampler import (GraphSageSampler, MixedGraphSageSampler, SampleJob,
-                           Adj, LinkBatch, TemporalBatch)
+                           Adj, LinkBatch, TemporalBatch,
+                           SubgraphBatch)
 
 __all__ = ["GraphSageSampler", "MixedGraphSageSampler", "SampleJob", "Adj",
-           "LinkBatch", "TemporalBatch"]
+           "LinkBatch", "TemporalBatch", "SubgraphBatch"]

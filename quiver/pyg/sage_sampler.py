@@ -22,7 +22,7 @@ T_co = TypeVar("T_co", covariant=True)
 T = TypeVar("T")
 
 __all__ = ["GraphSageSampler", "MixedGraphSageSampler", "SampleJob", "Adj",
-           "LinkBatch", "TemporalBatch"]
+           "LinkBatch", "TemporalBatch", "SubgraphBatch"]
 
 # attribute name, shared with quiver.nn and quiver.loader
 DST_PTR_ATTR = "_quiver_dst_ptr"
@@ -64,6 +64,13 @@ class TemporalBatch(NamedTuple):
     batch_size: int         # number of seeds (not deduplicated)
     adjs: list              # as sample()
     batch: torch.Tensor     # int64 [len(n_id)]: seed index of each entry's tree
+
+
+class SubgraphBatch(NamedTuple):
+    """What GraphSageSampler.subgraph and sample_saint_rw return."""
+    n_id: torch.Tensor          # int64 [n] distinct ids, first-occurrence order
+    edge_index: torch.Tensor    # int64 [2, m] local ids, sorted by row 1
+    e_id: torch.Tensor          # int64 [m] with return_eid, else empty
 
 
 @dataclass(frozen=True)
@@ -471,6 +478,69 @@ class GraphSageSampler:
             if self.mode == "CPU":
                 return self.quiver.random_walk(*args, self.return_eid)
             return self.quiver.random_walk(*args)
+
+    def subgraph(self, nodes):
+        """The graph between the nodes of a set: every stored edge with
+        both ends in `nodes`.
+
+        Args:
+            nodes: int64 [B] node ids, a tensor (CPU or GPU) or a list;
+                duplicates are allowed.
+
+        Returns SubgraphBatch(n_id, edge_index, e_id) on the sampler's
+        device.  `n_id` holds the distinct nodes in first-occurrence order.
+        `edge_index` is int64 [2, m] of local ids into `n_id`, one column
+        per CSR slot s of a row u in `n_id` whose indices[s] is in `n_id`
+        too: edge_index[1] is the local id of u, the message target as in
+        :meth:`sample`, edge_index[0] that of indices[s].  Columns ascend
+        in edge_index[1], then in CSR slot; an edge stored several times
+        appears several times and self-loops are kept.  The segment pointer
+        of edge_index[1] (int64 [n + 1]) hangs on `edge_index`, so
+        `sorted_dst=True` layers take `(x[n_id], x[n_id])`, `edge_index`
+        and size `(n, n)` as they are.  `e_id` is int64 [m], ids as in
+        `Adj.e_id`, on a sampler built with return_eid=True, else empty.
+
+        Nothing is drawn: the result depends on the graph and `n_id` only.
+        `edge_weight` is ignored; with `edge_time` the rows are the
+        time-sorted ones and there is no time bound.  An id outside the
+        graph raises ValueError, on a CPU input before anything is
+        launched, on a GPU input after the call's one host sync, which
+        reads the sizes.  Because of that sync the call cannot be captured
+        into a graph.
+        """
+        self.lazy_init_quiver()
+        if not isinstance(nodes, torch.Tensor):
+            nodes = torch.tensor(nodes, dtype=torch.long)
+        self._check_ids(nodes, "nodes", (None,))
+        nodes = nodes.to(self.device).contiguous()
+        with trace_scope("sampler.subgraph"):
+            if self.mode == "CPU":
+                n_id, edges, dst_ptr = self.quiver.subgraph(
+                    nodes, self.return_eid)
+            else:
+                n_id, edges, dst_ptr = self.quiver.subgraph(nodes)
+        if self.return_eid:
+            edge_index, e_id = edges[:2], edges[2]
+        else:
+            edge_index, e_id = edges, n_id.new_empty(0)
+        _attach_dst_ptr(edge_index, dst_ptr)
+        return SubgraphBatch(n_id, edge_index, e_id)
+
+    def sample_saint_rw(self, roots, walk_length, p=1.0, q=1.0):
+        """A GraphSAINT random-walk batch: the induced subgraph of the
+        nodes visited by one walk of `walk_length` steps from every root.
+
+        :meth:`random_walk` draws the walks (arguments as there), a walk
+        that has ended stays at its own root, and :meth:`subgraph` extracts
+        the edges between the visited nodes, so the distinct roots lead
+        `n_id` in their order.  Returns a SubgraphBatch.  GraphSAINT's
+        normalisation coefficients (node and edge appearance counts over
+        many batches) are not computed here.
+        """
+        walk, _ = self.random_walk(roots, walk_length, p, q)
+        walk = torch.where(walk < 0, walk[:, :1], walk)
+        # column-major: all the roots, then every walk's first step, ...
+        return self.subgraph(walk.t().reshape(-1))
 
     def sample_links(self, edge_label_index, num_neg=1, neg_tries=16,
                      edge_label_time=None):
