@@ -388,6 +388,89 @@ def bench_subgraph(mode, shape, topo, iters=10, repeats=7, warmup=2,
     return res
 
 
+ROW_BYTES = 400     # a feature row of bench.py's products preset: 100 fp32
+
+
+def bench_labor(mode, shape, topo, layer_dependency=False, batch=1024,
+                iters=10, repeats=7, warmup=2, device=0, passes=3,
+                chunks=(64, 256, 1024)):
+    """sample_labor beside plain sample() on the same seed batches: the
+    public call, the engine with either fill pass (hit mask, hashing again)
+    and at every built chunk size, and, for the cost of a hub row, batches
+    of 1024 seeds with and without node 0 (the graph's longest row).  Each
+    repeat times `passes` rounds over `iters` batches for each in turn;
+    reported are the median and the min..max over the repeats in ms per
+    batch and, as means over the batches, the edges of every hop (hop 0
+    first), n_id.numel(), the bytes a gather of n_id moves at ROW_BYTES a
+    row, and the ratio of the two methods' n_id sizes."""
+    cfg = SHAPES[shape]
+    sizes = cfg["fanout"]
+    sampler = quiver.GraphSageSampler(topo, sizes, device=device, mode=mode)
+    sampler.lazy_init_quiver()
+    eng, ld = sampler.quiver, bool(layer_dependency)
+    dev = f"cuda:{device}"
+    sync = torch.cuda.synchronize
+    g = torch.Generator().manual_seed(7)
+    seeds = [torch.randint(0, cfg["train"], (batch,), generator=g).to(dev)
+             for _ in range(iters)]
+    no_hub = [1 + torch.randint(0, cfg["nodes"] - 1, (1024,), generator=g)
+              .to(dev) for _ in range(iters)]
+    hub = [torch.cat([s.new_zeros(1), s[1:]]) for s in no_hub]
+
+    def labor(s):
+        return sampler.sample_labor(s, ld)
+
+    parts = dict(sample=(sampler.sample, seeds), labor=(labor, seeds))
+    for v, name in ((1, "labor_mask_fill"), (0, "labor_rehash_fill")):
+        parts[name] = (lambda s, v=v: eng.sample_labor_hops(
+            s, sizes, ld, 0, v), seeds)
+    for c in chunks:
+        parts[f"labor_chunk_{c}"] = (lambda s, c=c: eng.sample_labor_hops(
+            s, sizes, ld, c), seeds)
+    parts["labor_no_hub_1k"] = (labor, no_hub)
+    parts["labor_hub_1k"] = (labor, hub)
+    for fn, args_list in parts.values():
+        _timed(fn, args_list[:warmup], sync)
+    ms = {k: [] for k in parts}
+    for _ in range(repeats):
+        for k, (fn, args_list) in parts.items():
+            ms[k].append(_timed(fn, args_list * passes, sync))
+    res = dict(mode=mode, shape=shape, labor=True, layer_dependency=ld,
+               batch=batch, iters=iters, passes=passes, repeats=repeats,
+               default_chunk=quiver._ext.labor_chunk_slots(),
+               default_mask_fill=quiver._ext.labor_mask_fill(mode == "GPU"))
+    for k, v in ms.items():
+        res[k + "_ms"] = _stats(v)
+    for k in ("sample", "labor", "labor_no_hub_1k", "labor_hub_1k"):
+        fn, args_list = parts[k]
+        outs = [fn(s) for s in args_list]
+        n_id = float(np.mean([o[0].numel() for o in outs]))
+        res[k + "_sizes"] = dict(
+            edges_per_hop=np.mean([[a.edge_index.size(1) for a in o[2][::-1]]
+                                   for o in outs], axis=0).tolist(),
+            n_id=n_id, gather_bytes=n_id * ROW_BYTES)
+    res["n_id_ratio"] = (res["labor_sizes"]["n_id"]
+                         / res["sample_sizes"]["n_id"])
+    if mode == "UVA":
+        # what the mask fill reads of the pinned rows: every long row once,
+        # and 8 B for every edge of the batch (a whole row is read by the
+        # fill pass alone)
+        degree = topo.degree.to(dev)
+        slots = []
+        for s in seeds:
+            n_id, _, adjs = labor(s)
+            rows, total = s, 0
+            for adj, k in zip(adjs[::-1], sizes):
+                d = degree[rows]
+                total += int(d[d > k].sum()) + adj.edge_index.size(1)
+                rows = n_id[:int(adj.size[0])]
+            slots.append(total)
+        res["host_bytes_read"] = 8 * float(np.mean(slots))
+        res["host_gbps"] = res["host_bytes_read"] / (
+            res["labor_ms"]["median"] * 1e-3) / 1e9
+    return res
+
+
 if __name__ == "__main__":
     p = argparse.ArgumentParser()
     p.add_argument("--modes", default="UVA,GPU,CPU")
@@ -424,7 +507,29 @@ if __name__ == "__main__":
                         "uniform nodes, a set with and without the hub row; "
                         "chunks of 64, 256 and 1024 slots) in GPU and UVA "
                         "mode, beside a plain-torch version in GPU mode")
+    p.add_argument("--labor", action="store_true",
+                   help="time sample_labor (either fill pass, chunks of 64, "
+                        "256 and 1024 slots, a batch with and without the "
+                        "hub row) beside plain sample() on the same seeds in "
+                        "GPU and UVA mode, with the sizes of both methods' "
+                        "batches")
+    p.add_argument("--layer-dependency", action="store_true",
+                   help="with --labor: one variate per node for all hops")
     args = p.parse_args()
+    if args.labor:
+        assert torch.cuda.is_available(), "--labor needs a GPU"
+        for shape in args.shapes.split(","):
+            cfg = SHAPES[shape]
+            indptr, indices = make_graph(cfg["nodes"], cfg["edges"])
+            topo = quiver.CSRTopo(indptr=indptr, indices=indices)
+            for mode in args.modes.split(","):
+                if mode == "CPU":       # timed on the GPU only
+                    continue
+                print(json.dumps(bench_labor(
+                    mode, shape, topo, args.layer_dependency,
+                    batch=args.batch, iters=min(args.iters, 10),
+                    repeats=args.repeats)), flush=True)
+        sys.exit(0)
     if args.subgraph:
         assert torch.cuda.is_available(), "--subgraph needs a GPU"
         for shape in args.shapes.split(","):

@@ -21,6 +21,7 @@ KERNEL_SOURCES = [
     "sample_kernels.hip",
     "reindex_kernels.hip",
     "subgraph_kernels.hip",
+    "labor_kernels.hip",
     "gather_kernels.hip",
     "segment_kernels.hip",
     "gatv2_kernels.hip",
@@ -28,7 +29,7 @@ KERNEL_SOURCES = [
     "gemm_kernels.hip",
 ]
 TORCH_SOURCES = ["module.cpp"]
-HEADERS = ["qk_common.h", "segment_io.h", "hash_probe.h"]
+HEADERS = ["qk_common.h", "segment_io.h", "hash_probe.h", "rng_hash.h"]
 # per-file extra flags.  gatv2, sample: keep the compiler from pairing fp32
 # math into packed two-wide instructions (scalar fp32 ops only).
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]

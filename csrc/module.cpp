@@ -615,6 +615,124 @@ class GpuSampler {
         return res;
     }
 
+    // LABOR-0 layer-neighbour sampling, the contract at LaborHop: per hop
+    // (frontier, edges, dst_ptr) as sample_hops_ptr returns them, fanouts
+    // >= 1 or -1 for whole rows.  Hop h draws with salt (h + 1) *
+    // 0x632be59bd9b4e019 on the RNG word after one bump, or with salt 0 at
+    // every hop under `layer_dependency` (one variate per node and batch).
+    // A hop's edge count has no bound known beforehand, so every hop syncs
+    // twice on a device-to-host copy of sizes: {edges, chunks}, then the
+    // distinct count.  Only input nodes given several times can make the
+    // chunks outgrow their host bound (rows distinct as every later
+    // frontier's add up to the graph's slots at most); the hop is then
+    // counted again with the exact bound, at the cost of one more copy.
+    // `chunk_slots` (0: the default) and `mask_fill` (-1: the default of
+    // the graph's placement) are for tuning only.
+    std::vector<std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>>
+    sample_labor_hops(torch::Tensor nodes, const std::vector<int>& ks,
+                      bool layer_dependency, int chunk_slots, int mask_fill) {
+        DeviceScope g(device_);
+        auto stream = current_stream();
+        TORCH_CHECK(nodes.dtype() == torch::kInt64, "nodes must be int64");
+        TORCH_CHECK(nodes.device().is_cuda() &&
+                        nodes.device().index() == device_,
+                    "nodes must be on the sampler's GPU");
+        TORCH_CHECK(nodes.dim() == 1 && nodes.is_contiguous(),
+                    "nodes must be a contiguous 1-D tensor");
+        for (int k : ks)
+            TORCH_CHECK(k >= 1 || k == -1,
+                        "sample_labor: fanouts must be >= 1, or -1");
+        if (weight_dptr_)
+            throw py::value_error("sample_labor: there is no edge-weighted "
+                                  "LABOR draw");
+        const int chunk =
+            chunk_slots > 0 ? chunk_slots : qk::labor_chunk_slots();
+        const bool use_mask =
+            mask_fill < 0 ? qk::labor_mask_fill(dma_) : mask_fill != 0;
+        auto opts = nodes.options();
+        const int64_t rows_out = emit_eid_ ? 3 : 2;
+        qk::launch_rng_bump(stream, rng_dev(stream));
+
+        std::vector<std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>>
+            res;
+        torch::Tensor cur = nodes;
+        for (size_t h = 0; h < ks.size(); ++h) {
+            const int64_t n = cur.numel();
+            if (n == 0) {
+                res.emplace_back(cur, torch::empty({rows_out, 0}, opts),
+                                 torch::zeros({1}, opts));
+                continue;
+            }
+            // {m, chunks, distinct}
+            auto sizes = torch::empty({3}, opts);
+            int64_t* sd = sizes.data_ptr<int64_t>();
+            qk::LaborHop p = {};
+            p.indptr = indptr_.data_ptr<int64_t>();
+            p.indices = indices_dptr_;
+            p.eid = eid_dptr_;
+            p.node_count = node_count_;
+            p.rows = cur.data_ptr<int64_t>();
+            p.n = n;
+            p.k = ks[h];
+            p.chunk = chunk;
+            p.salt = layer_dependency
+                         ? 0 : (uint64_t)(h + 1) * 0x632be59bd9b4e019ULL;
+            p.rng = rng_dev(stream);
+            p.chunks_dev = sd + 1;
+            p.chunk_ub = n + indices_.numel() / chunk;
+
+            torch::Tensor counts, row_first, chunk_count, mask, chunk_off,
+                prefix;
+            int64_t m = 0;
+            while (true) {
+                counts = torch::empty({n + 1}, opts);
+                auto row_chunks = torch::empty({n + 1}, opts);
+                p.counts = counts.data_ptr<int64_t>();
+                qk::launch_labor_rows(stream, p,
+                                      row_chunks.data_ptr<int64_t>());
+                row_first = exclusive_scan(row_chunks, sd + 1, stream);
+                p.row_first = row_first.data_ptr<int64_t>();
+                chunk_count = torch::empty({p.chunk_ub + 1}, opts);
+                p.chunk_count = chunk_count.data_ptr<int64_t>();
+                if (use_mask) {
+                    mask = torch::empty({p.chunk_ub * (chunk / 64) + 1}, opts);
+                    p.mask = (unsigned long long*)mask.data_ptr<int64_t>();
+                }
+                qk::launch_labor_count(stream, p);
+                chunk_off = exclusive_scan(chunk_count, nullptr, stream);
+                // the scan of the per-row counts is the hop's dst_ptr
+                prefix = exclusive_scan(counts, sd, stream);
+                auto host = sizes.narrow(0, 0, 2).cpu();    // sync 1
+                m = host.data_ptr<int64_t>()[0];
+                const int64_t chunks = host.data_ptr<int64_t>()[1];
+                if (chunks <= p.chunk_ub) break;
+                p.chunk_ub = chunks;
+            }
+            // the node table keeps first positions as int32
+            TORCH_CHECK(n + m < INT32_MAX, "sample_labor: hop too large");
+            auto edges = torch::empty({rows_out, m}, opts);
+            auto out = torch::empty({m}, opts);
+            int64_t* ep = edges.data_ptr<int64_t>();
+            p.chunk_off = chunk_off.data_ptr<int64_t>();
+            p.prefix = prefix.data_ptr<int64_t>();
+            p.m = m;
+            p.out_nbr = out.data_ptr<int64_t>();
+            p.out_id = emit_eid_ ? ep + 2 * m : nullptr;
+            qk::launch_labor_fill(stream, p);
+
+            auto table = reindex_build(stream, p.rows, n, p.out_nbr, m,
+                                       nullptr, nullptr, sd + 2, opts);
+            const int64_t u = sizes.narrow(0, 2, 1).cpu()       // sync 2
+                                  .data_ptr<int64_t>()[0];
+            auto frontier = torch::empty({u}, opts);
+            reindex_finish(stream, table, p.prefix, p.counts,
+                           frontier.data_ptr<int64_t>(), ep, ep + m);
+            res.emplace_back(frontier, edges, prefix);
+            cur = frontier;
+        }
+        return res;
+    }
+
     void cal_neighbor_prob(int /*stream_id*/, torch::Tensor last_prob,
                            torch::Tensor cur_prob, int k) {
         DeviceScope g(device_);
@@ -1055,8 +1173,10 @@ class CpuSampler {
 
     // The seed of random_walk, which draws from stateless streams keyed by
     // (seed, walk row, step) like the GPU engine, so a call does not depend
-    // on how its walks are spread over threads.  The other draws of this
-    // engine keep their per-thread generators.
+    // on how its walks are spread over threads, and of sample_labor_hops,
+    // keyed by (seed, hop, node).  Each call of either advances it by the
+    // golden-ratio step first, as the GPU engine's word.  The other draws
+    // of this engine keep their per-thread generators.
     void set_seed(uint64_t seed) { walk_seed_.store(seed); }
 
     // Random walks, the contract of launch_random_walk: (walk int64 [n,
@@ -1208,6 +1328,113 @@ class CpuSampler {
         auto n_id = torch::empty({n}, nodes.options());
         std::copy(set.begin(), set.end(), n_id.data_ptr<int64_t>());
         return {n_id, edges, dst_ptr};
+    }
+
+    // LABOR-0 layer-neighbour sampling, the contract, the variate and the
+    // output of GpuSampler::sample_labor_hops, element for element: the
+    // call word follows the rule of the device RNG word (set_seed, one
+    // bump a call).  A count pass and a fill pass over the rows, then a
+    // first-occurrence reindex.
+    std::vector<std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>>
+    sample_labor_hops(torch::Tensor nodes, const std::vector<int>& ks,
+                      bool layer_dependency, bool want_ids) {
+        TORCH_CHECK(nodes.dtype() == torch::kInt64, "nodes must be int64");
+        TORCH_CHECK(nodes.device().is_cpu(), "nodes must be a CPU tensor");
+        TORCH_CHECK(nodes.dim() == 1 && nodes.is_contiguous(),
+                    "nodes must be a contiguous 1-D tensor");
+        for (int k : ks)
+            TORCH_CHECK(k >= 1 || k == -1,
+                        "sample_labor: fanouts must be >= 1, or -1");
+        if (weight_.defined())
+            throw py::value_error("sample_labor: there is no edge-weighted "
+                                  "LABOR draw");
+        const int64_t* indptr = indptr_.data_ptr<int64_t>();
+        const int64_t* indices = indices_.data_ptr<int64_t>();
+        const int64_t* eid = eid_.defined() ? eid_.data_ptr<int64_t>()
+                                            : nullptr;
+        constexpr uint64_t kGolden = 0x9e3779b97f4a7c15ULL;
+        const uint64_t word = walk_seed_.fetch_add(kGolden) + kGolden;
+        auto hash = [](uint64_t x) {            // SplitMix64
+            x += 0x9e3779b97f4a7c15ULL;
+            x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ULL;
+            x = (x ^ (x >> 27)) * 0x94d049bb133111ebULL;
+            return x ^ (x >> 31);
+        };
+        for (int64_t i = 0; i < nodes.numel(); ++i) {
+            const int64_t v = nodes.data_ptr<int64_t>()[i];
+            if (v < 0 || v >= node_count_)
+                throw py::value_error(
+                    "sample_labor: node " + std::to_string(v) +
+                    " lies outside [0, " + std::to_string(node_count_) + ")");
+        }
+        std::vector<std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>>
+            res;
+        torch::Tensor cur = nodes;
+        for (size_t h = 0; h < ks.size(); ++h) {
+            const int64_t n = cur.numel(), k = ks[h];
+            const int64_t* cp = cur.data_ptr<int64_t>();
+            const uint64_t key = hash(
+                word + (layer_dependency
+                            ? 0 : (uint64_t)(h + 1) * 0x632be59bd9b4e019ULL));
+            auto keep = [&](int64_t s, int64_t deg) {
+                const uint64_t r = hash(key + (uint64_t)indices[s] * kGolden);
+                return (uint64_t)(((unsigned __int128)r * (uint64_t)deg)
+                                  >> 64) < (uint64_t)k;
+            };
+            auto dst_ptr = torch::zeros({n + 1}, nodes.options());
+            int64_t* dp = dst_ptr.data_ptr<int64_t>();
+            at::parallel_for(0, n, 64, [&](int64_t b, int64_t e) {
+                for (int64_t i = b; i < e; ++i) {
+                    const int64_t beg = indptr[cp[i]];
+                    const int64_t deg = indptr[cp[i] + 1] - beg;
+                    int64_t kept = deg;
+                    if (k >= 0 && deg > k) {
+                        kept = 0;
+                        for (int64_t s = beg; s < beg + deg; ++s)
+                            kept += keep(s, deg);
+                    }
+                    dp[i + 1] = kept;
+                }
+            });
+            for (int64_t i = 0; i < n; ++i) dp[i + 1] += dp[i];
+            const int64_t m = dp[n];
+            auto edges = torch::empty({want_ids ? 3 : 2, m}, nodes.options());
+            int64_t* ep = edges.data_ptr<int64_t>();
+            std::vector<int64_t> out(m);
+            at::parallel_for(0, n, 64, [&](int64_t b, int64_t e) {
+                for (int64_t i = b; i < e; ++i) {
+                    const int64_t beg = indptr[cp[i]];
+                    const int64_t deg = indptr[cp[i] + 1] - beg;
+                    const bool whole = k < 0 || deg <= k;
+                    int64_t at = dp[i];
+                    for (int64_t s = beg; s < beg + deg; ++s) {
+                        if (!whole && !keep(s, deg)) continue;
+                        out[at] = indices[s];
+                        ep[m + at] = i;
+                        if (want_ids) ep[2 * m + at] = eid ? eid[s] : s;
+                        ++at;
+                    }
+                }
+            });
+            std::unordered_map<int64_t, int64_t> local;
+            local.reserve(2 * (n + m));
+            std::vector<int64_t> frontier;
+            for (int64_t i = 0; i < n; ++i)
+                if (local.emplace(cp[i], (int64_t)frontier.size()).second)
+                    frontier.push_back(cp[i]);
+            for (int64_t j = 0; j < m; ++j) {
+                auto it = local.emplace(out[j], (int64_t)frontier.size());
+                if (it.second) frontier.push_back(out[j]);
+                ep[j] = it.first->second;
+            }
+            auto fr = torch::empty({(int64_t)frontier.size()},
+                                   nodes.options());
+            std::copy(frontier.begin(), frontier.end(),
+                      fr.data_ptr<int64_t>());
+            res.emplace_back(fr, edges, dst_ptr);
+            cur = fr;
+        }
+        return res;
     }
 
     std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> reindex_single(
@@ -2728,6 +2955,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("sample_hops_raw", &GpuSampler::sample_hops_raw,
              py::call_guard<py::gil_scoped_release>(),
              "zero-sync variant: ub-sized tensors + device sizes vector")
+        .def("sample_labor_hops", &GpuSampler::sample_labor_hops,
+             py::arg("nodes"), py::arg("sizes"),
+             py::arg("layer_dependency") = false, py::arg("chunk_slots") = 0,
+             py::arg("mask_fill") = -1,
+             py::call_guard<py::gil_scoped_release>(),
+             "LABOR-0 layer-neighbour sampling, two syncs a hop: per hop "
+             "(frontier, edges [2 or 3, m], dst_ptr); chunk_slots and "
+             "mask_fill are for tuning")
         .def("reindex_single", &GpuSampler::reindex_single,
              py::call_guard<py::gil_scoped_release>())
         .def("cal_neighbor_prob", &GpuSampler::cal_neighbor_prob,
@@ -2768,8 +3003,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              py::call_guard<py::gil_scoped_release>(),
              "induced subgraph of a node set: (n_id, edges [2 or 3, m], "
              "dst_ptr [n + 1]); ValueError on an id outside the graph")
+        .def("sample_labor_hops", &CpuSampler::sample_labor_hops,
+             py::arg("nodes"), py::arg("sizes"),
+             py::arg("layer_dependency") = false, py::arg("want_ids") = false,
+             py::call_guard<py::gil_scoped_release>(),
+             "LABOR-0 layer-neighbour sampling: per hop (frontier, edges "
+             "[2 or 3, m], dst_ptr)")
         .def("set_seed", &CpuSampler::set_seed,
-             "seed of random_walk (the other draws have none)")
+             "seed of random_walk and sample_labor_hops (the other draws "
+             "have none)")
         .def("set_edge_time", &CpuSampler::set_edge_time,
              py::arg("time_csr"), py::arg("emit_eid") = false,
              "int64 edge times, one per CSR slot, every row ascending")
@@ -2850,6 +3092,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("segment_mean_rows_in_flight", &qk::segment_mean_rows_in_flight);
     m.def("subgraph_chunk_slots", &qk::subgraph_chunk_slots,
           "CSR slots per unit of work of the subgraph kernels");
+    m.def("labor_chunk_slots", &qk::labor_chunk_slots,
+          "CSR slots per unit of work of the LABOR kernels");
+    m.def("labor_mask_fill", &qk::labor_mask_fill, py::arg("graph_in_hbm"),
+          "whether the LABOR fill pass reads the count pass's hit mask "
+          "(else it hashes again), by placement of the graph");
 
     m.def("tall_gemm", &tall_gemm,
           "C[M,N] = A[M,K] @ B[K,N] (+bias), M huge, MFMA 32x32 tiles");

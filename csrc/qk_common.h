@@ -10,6 +10,7 @@
 //   sample_kernels.hip   neighbour sampling, scans, access probabilities
 //   reindex_kernels.hip  hash-table frontier reindex
 //   subgraph_kernels.hip induced subgraph of a node set
+//   labor_kernels.hip    LABOR-0 layer-neighbour sampling
 //   gather_kernels.hip   sharded feature gather / scatter
 //   gemm_kernels.hip     tall-M GEMM
 //   wgrad_kernels.hip    tall-skinny split-K weight gradient
@@ -254,6 +255,58 @@ void launch_subgraph_fill(hipStream_t s, const SubgraphSet& g,
                           const ReindexSet& table, int64_t n, int64_t m,
                           int64_t* out_src, int64_t* out_dst, int64_t* out_id,
                           int64_t* dst_ptr);
+
+// ---------- LABOR-0 layer-neighbour sampling (labor_kernels.hip) ----------
+//
+// One hop over the rows of `rows` with fanout k: a row of degree d <= k
+// (or k == -1) keeps all its slots, a longer one the slots j with
+//   umulhi(splitmix64(key + indices[j] * 0x9e3779b97f4a7c15), d) < k,
+//   key = splitmix64(*rng + salt),
+// so one variate per source node serves every row of the hop.  The caller
+// runs, on one stream: rows, a scan of row_chunks (-> row_first,
+// *chunks_dev), count, a scan of chunk_count (-> chunk_off) and one of
+// counts (-> prefix, the hop's dst_ptr, and the edge total m), a sync for
+// m, fill.  A chunk is up to `chunk` consecutive slots of one row and the
+// unit of work of count and fill.
+struct LaborHop {
+    const int64_t* indptr;
+    const int64_t* indices;
+    const int64_t* eid;           // null: an edge's id is its CSR slot
+    int64_t node_count;
+    const int64_t* rows;          // [n] node ids; one outside the graph is
+    int64_t n;                    //   an empty row.  n is exact, >= 1
+    int k;                        // >= 1, or -1 for whole rows
+    int chunk;                    // 64, 256 or 1024
+    uint64_t salt;
+    const uint64_t* rng;          // the engine's RNG word (device)
+    const int64_t* row_first;     // [n + 1] exclusive scan of row_chunks
+    const int64_t* chunks_dev;    // sum of row_chunks (device)
+    int64_t chunk_ub;             // host bound of it; chunks past it are
+                                  //   left out (the caller compares)
+    int64_t* counts;              // [n + 1] kept slots of every row, [n] = 0
+    int64_t* chunk_count;         // [chunk_ub + 1]; entries from *chunks_dev
+                                  //   on are not written
+    unsigned long long* mask;     // [chunk_ub * chunk / 64] hit bits, bit j
+                                  //   % 64 of word j / 64 for a chunk's
+                                  //   slot j, written by count and read by
+                                  //   fill; null: fill hashes again
+    // fill only
+    const int64_t* chunk_off;     // [chunk_ub + 1] scanned chunk_count
+    const int64_t* prefix;        // [n + 1] scanned counts
+    int64_t m;                    // edges in all
+    int64_t* out_nbr;             // [m] kept neighbours (global ids), rows
+                                  //   in order, slots in CSR order
+    int64_t* out_id;              // [m] their edge ids; null: none
+};
+// slots per chunk the engine uses, and whether its fill pass reads the hit
+// mask, by placement of the graph (HBM, or pinned host memory)
+int labor_chunk_slots();
+bool labor_mask_fill(bool graph_in_hbm);
+// counts[i] = degree of a whole row, 0 for a longer one (count adds its
+// chunks' hits); row_chunks[i] = ceil(degree / chunk); n + 1 entries each.
+void launch_labor_rows(hipStream_t s, const LaborHop& p, int64_t* row_chunks);
+void launch_labor_count(hipStream_t s, const LaborHop& p);
+void launch_labor_fill(hipStream_t s, const LaborHop& p);
 
 // ---------- feature gather (gather_kernels.hip) ----------
 

@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "qk_common.h"
+#include "rng_hash.h"
 
 namespace qk {
 
@@ -24,13 +25,6 @@ namespace {
 constexpr int BLOCK = 256;
 constexpr int SUB = 16;                    // lanes per seed row
 constexpr int ROWS_PER_BLOCK = BLOCK / SUB;
-
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-    x += 0x9e3779b97f4a7c15ULL;
-    x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    x = (x ^ (x >> 27)) * 0x94d049bb133111ebULL;
-    return x ^ (x >> 31);
-}
 
 // Unbiased-enough bounded random for bound up to 2^31: take high bits.
 __device__ __forceinline__ int64_t bounded_rand(uint64_t h, int64_t bound) {
@@ -300,14 +294,9 @@ weighted_sample_kernel(const int64_t* __restrict__ indptr,
 
 // ---- negative tails for link prediction -----------------------------------
 
-// Uniform in [0, bound): the high 64 bits of h * bound, h the full 64-bit
-// hash.  Not bounded_rand: its (h >> 11) * bound is a 53-bit value times
-// the bound and overflows 64 bits once the bound exceeds 2048, and here the
-// bound is the node count.  The 128-bit product cannot overflow for any
-// bound, and its bias is bound / 2^64 (under 2^-24 up to 2^40 nodes).
-__device__ __forceinline__ int64_t mulhi_rand(uint64_t h, uint64_t bound) {
-    return (int64_t)__umul64hi(h, bound);
-}
+// Candidates are drawn with mulhi_rand (rng_hash.h), not bounded_rand: its
+// (h >> 11) * bound is a 53-bit value times the bound and overflows 64 bits
+// once the bound exceeds 2048, and here the bound is the node count.
 
 constexpr int kNegAhead = 4;   // 16-wide steps of a row loaded together
 

@@ -309,6 +309,65 @@ class GraphSageSampler:
             nodes = frontier
         return nodes, batch_size, adjs[::-1]
 
+    def sample_labor(self, input_nodes, layer_dependency=False):
+        """Sample a k-hop computational graph by LABOR-0 layer-neighbour
+        sampling (Balin and Catalyurek, NeurIPS 2023).
+
+        In one hop every candidate source node t has a single variate,
+        shared by all rows of the hop.  A row of degree d <= k, the hop's
+        fanout (or any row when k == -1), keeps all its edges; a longer
+        one keeps the edge from t iff that variate falls below k / d.
+        Every edge of a row is kept with the same probability k / d, so a
+        row keeps k edges in expectation, maybe none, and an edge stored
+        twice is kept twice or not at all.  The mean over the kept edges
+        estimates the row's mean as in :meth:`sample` (no edge weights
+        are needed), but a source is kept for all rows of similar degree
+        or for none, so `n_id` holds fewer distinct nodes.
+
+        Returns (n_id, batch_size, adjs) laid out as :meth:`sample` returns
+        them, `dst_ptr` attached to every edge_index.  Columns ascend in
+        the target's local id, then in CSR slot; `n_id` keeps the previous
+        frontier as its prefix, new sources follow in first-occurrence
+        order.  `layer_dependency=True` gives a node the same variate at
+        every hop of the batch.  The README states the variate exactly;
+        `sampler.quiver.set_seed(S)` fixes it, and CPU, GPU and UVA mode
+        then return identical batches.
+
+        Each hop synchronises with the host twice (its edge count has no
+        bound known beforehand), so the call cannot be captured into a
+        graph.  A sampler built with `edge_weight` raises ValueError; with
+        `edge_time` the whole graph is sampled over the time-sorted rows.
+        Ids are range-checked on a CPU input only; on a GPU input an id
+        outside the graph is an empty row.
+        """
+        if self.w_csr_ is not None:
+            raise ValueError("sample_labor on a sampler built with "
+                             "edge_weight: there is no weighted LABOR draw")
+        if not all(s > 0 or s == -1 for s in self.sizes):
+            raise ValueError(f"fanouts must be > 0, or -1: {self.sizes}")
+        self.lazy_init_quiver()
+        if not isinstance(input_nodes, torch.Tensor):
+            input_nodes = torch.tensor(input_nodes, dtype=torch.long)
+        self._check_ids(input_nodes, "input_nodes", (None,))
+        nodes = input_nodes.to(self.device).contiguous()
+        sizes = [int(s) for s in self.sizes]
+        with trace_scope("sampler.sample_labor"):
+            if self.mode == "CPU":
+                hops = self.quiver.sample_labor_hops(
+                    nodes, sizes, bool(layer_dependency), self.return_eid)
+            else:
+                hops = self.quiver.sample_labor_hops(
+                    nodes, sizes, bool(layer_dependency))
+        adjs = []
+        frontier, prev_n = nodes, nodes.size(0)
+        for frontier, edges, dst_ptr in hops:
+            edge_index, e_id = self._split_edges(edges)
+            _attach_dst_ptr(edge_index, dst_ptr)
+            adj_size = torch.LongTensor([frontier.size(0), prev_n])
+            adjs.append(Adj(edge_index, e_id, adj_size))
+            prev_n = frontier.size(0)
+        return frontier, nodes.size(0), adjs[::-1]
+
     def sample_temporal(self, seeds, seed_time):
         """Sample one k-hop tree per seed that holds only edges which
         existed by the seed's time bound.
