@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""One GATv2Conv layer, fused kernels against the layer's torch chain.
+"""One GATv2Conv (or TransformerConv) layer, fused kernels against the
+layer's torch chain.
 
 Shapes: the hidden layers of `bench.py --model gat` on products (heads 4,
 64 channels per head, 256 input channels) at synthetic frontier sizes for
@@ -16,8 +17,11 @@ Both paths get the same parameters and inputs; their outputs are compared.
 
 --edge-dim D gives both layers edge_dim=D and a random [E, D] edge_attr in
 the row dtype (one row per edge); --shapes picks rows of SHAPES by index.
+--layer transformer measures TransformerConv (beta=False, root_weight=True,
+PyG's defaults) the same way; it takes no edge features.
 
-  python benchmarks/bench_gatv2.py [--md FILE] [--edge-dim D] [--shapes I..]
+  python benchmarks/bench_gatv2.py [--layer gatv2|transformer] [--md FILE]
+                                   [--edge-dim D] [--shapes I..]
 """
 import argparse
 import json
@@ -28,7 +32,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from quiver.nn import GATv2Conv  # noqa: E402
+from quiver.nn import GATv2Conv, TransformerConv  # noqa: E402
 from quiver.pyg.sage_sampler import DST_PTR_ATTR  # noqa: E402
 
 H, C, IN = 4, 64, 256
@@ -46,11 +50,11 @@ def make_inputs(n_dst, fanout, n_src, dtype):
     return x.requires_grad_(), ei
 
 
-def make_step(conv, x, ei, n_dst, backward, edge_attr=None):
+def make_step(conv, x, ei, n_dst, backward, fw):
     size = (x.size(0), n_dst)
 
     def step():
-        out = conv((x, x[:n_dst]), ei, size, edge_attr=edge_attr)
+        out = conv((x, x[:n_dst]), ei, size, **fw)
         if backward:
             x.grad = None
             conv.zero_grad(set_to_none=True)
@@ -86,8 +90,12 @@ def main():
     ap.add_argument("--shapes", type=int, nargs="+",
                     default=list(range(len(SHAPES))),
                     help="indices into SHAPES (default: all)")
+    ap.add_argument("--layer", choices=["gatv2", "transformer"],
+                    default="gatv2", help="which layer to measure")
     args = ap.parse_args()
     kw = {} if args.edge_dim is None else dict(edge_dim=args.edge_dim)
+    layer = GATv2Conv if args.layer == "gatv2" else TransformerConv
+    assert layer is GATv2Conv or not kw, "TransformerConv has no edge_dim"
     assert torch.cuda.is_available(), "bench_gatv2 needs a GPU"
     lines = ["| dtype | n_dst | fanout | n_src | mode | fused ms | chain ms |"
              " speedup | fused peak MiB | chain peak MiB |",
@@ -101,21 +109,20 @@ def main():
                                  generator=torch.Generator().manual_seed(1)
                                  ).to("cuda", dtype)
             torch.manual_seed(0)
-            convs = {"fused": GATv2Conv(IN, C, heads=H, sorted_dst=True,
-                                        **kw),
-                     "chain": GATv2Conv(IN, C, heads=H, sorted_dst=False,
-                                        **kw)}
+            fw = {} if ea is None else dict(edge_attr=ea)
+            convs = {"fused": layer(IN, C, heads=H, sorted_dst=True, **kw),
+                     "chain": layer(IN, C, heads=H, sorted_dst=False, **kw)}
             convs["chain"].load_state_dict(convs["fused"].state_dict())
             for c in convs.values():
                 c.to("cuda", dtype)
             with torch.no_grad():
                 a, b = (convs[k]((x, x[:n_dst]), ei, (n_src, n_dst),
-                                 edge_attr=ea).float()
+                                 **fw).float()
                         for k in ("fused", "chain"))
                 diff = ((a - b).abs().max() / b.abs().max()).item()
             del a, b
             for backward in (False, True):
-                steps = {k: make_step(c, x, ei, n_dst, backward, ea)
+                steps = {k: make_step(c, x, ei, n_dst, backward, fw)
                          for k, c in convs.items()}
                 iters = {}
                 for k, s in steps.items():

@@ -25,16 +25,19 @@ KERNEL_SOURCES = [
     "gather_kernels.hip",
     "segment_kernels.hip",
     "gatv2_kernels.hip",
+    "transformer_kernels.hip",
     "wgrad_kernels.hip",
     "gemm_kernels.hip",
 ]
 TORCH_SOURCES = ["module.cpp"]
-HEADERS = ["qk_common.h", "segment_io.h", "hash_probe.h", "rng_hash.h"]
-# per-file extra flags.  gatv2, sample: keep the compiler from pairing fp32
-# math into packed two-wide instructions (scalar fp32 ops only).
+HEADERS = ["qk_common.h", "segment_io.h", "segment_layout.h", "hash_probe.h",
+           "rng_hash.h"]
+# per-file extra flags.  gatv2, transformer, sample: keep the compiler from
+# pairing fp32 math into packed two-wide instructions (scalar fp32 ops only).
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
     "gatv2_kernels.hip": NO_PACKED_FP32,
+    "transformer_kernels.hip": NO_PACKED_FP32,
     "sample_kernels.hip": NO_PACKED_FP32,
 }
 OUT = os.path.join(ROOT, "torch_quiver.so")

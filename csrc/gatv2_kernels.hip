@@ -81,7 +81,7 @@
 // most 1024 slots (NCH <= 16): with 32 slots per lane p would spill.
 #include <algorithm>
 
-#include "segment_io.h"
+#include "segment_layout.h"
 
 namespace qk {
 
@@ -89,82 +89,6 @@ namespace {
 
 constexpr int BLOCK = 256;
 constexpr int MAX_DIM = 1024;  // heads * chead served by these kernels
-
-// One 4-byte word of a row in fp32 working precision.
-template <typename T> struct wordio;
-template <> struct wordio<float> {
-    using raw_t = float;
-    static constexpr int EPW = 1;
-    static __device__ __forceinline__ void unpack(raw_t w, float f[1]) {
-        f[0] = w;
-    }
-    static __device__ __forceinline__ float pack(const float f[1]) {
-        return f[0];
-    }
-};
-template <> struct wordio<__hip_bfloat16> {
-    using raw_t = uint32_t;
-    static constexpr int EPW = 2;
-    static __device__ __forceinline__ void unpack(raw_t w, float f[2]) {
-        f[0] = __uint_as_float(w << 16);
-        f[1] = __uint_as_float(w & 0xffff0000u);
-    }
-    static __device__ __forceinline__ __hip_bfloat162 pack(const float f[2]) {
-        return __float22bfloat162_rn(float2{f[0], f[1]});
-    }
-};
-
-constexpr int ilog2(int v) { return v <= 1 ? 0 : 1 + ilog2(v / 2); }
-
-// Slot map of one launch (see the header comment).
-struct Layout {
-    int heads;
-    int wph;    // words per head
-    int logp;   // slots per head = 1 << logp
-    int words;  // heads * wph
-};
-
-// Word index of each slot of this lane, -1 for a padding slot, and the
-// head it belongs to (>= heads for slots past the last head).
-template <int LANES, int NCH>
-__device__ __forceinline__ void slot_map(const Layout& L, int lane,
-                                         int widx[NCH], int head[NCH]) {
-#pragma unroll
-    for (int k = 0; k < NCH; ++k) {
-        const int slot = k * LANES + lane;
-        const int h = slot >> L.logp;
-        const int j = slot & ((1 << L.logp) - 1);
-        head[k] = h;
-        widx[k] = (h < L.heads && j < L.wph) ? h * L.wph + j : -1;
-    }
-}
-
-// p[k] <- sum of p over every slot of slot k's head, for all slots of the
-// group.  rs = log2 of the slots of one lane that share a head (0 unless a
-// head is wider than the group), bw = lanes spanned by one head.
-template <int LANES, int NCH>
-__device__ __forceinline__ void head_reduce(float p[NCH], int rs, int bw) {
-    // in-register tree: the lowest slot of each run of 2^rs takes the sum
-#pragma unroll
-    for (int t = 0; (1 << t) < NCH; ++t)
-#pragma unroll
-        for (int k = 0; k < NCH; ++k)
-            if (!(k & (1 << t)) && t < rs) p[k] += p[k | (1 << t)];
-    // butterfly across the lanes of the head, run leaders only
-    const int mask = (1 << rs) - 1;
-#pragma unroll
-    for (int k = 0; k < NCH; ++k) {
-        if ((k & mask) == 0)
-            for (int off = 1; off < bw; off <<= 1)
-                p[k] += __shfl_xor(p[k], off, LANES);
-    }
-    // hand the sum back down the tree
-#pragma unroll
-    for (int t = ilog2(NCH) - 1; t >= 0; --t)
-#pragma unroll
-        for (int k = 0; k < NCH; ++k)
-            if ((k & (1 << t)) && t < rs) p[k] = p[k ^ (1 << t)];
-}
 
 // rows in flight per group: ~16 words per lane in the forward, ~8 in the
 // backward (which also holds g_out and two more accumulators)
@@ -580,37 +504,6 @@ gatv2_attn_bwd_kernel(const T* __restrict__ grad_out,
     }
 }
 
-// Lane group and slots per lane for a row of `heads` heads of `chead`
-// channels: LANES = smallest power of two covering heads * P slots (2 ..
-// 64), NCH = power of two of slots per lane once the group is a full wave.
-struct Plan {
-    Layout L;
-    int lanes, nch;
-};
-
-Plan plan_for(const char* op, Elem et, int heads, int chead) {
-    if (heads < 1 || chead < 4 || chead % 4 != 0)
-        throw std::runtime_error(
-            std::string(op) +
-            ": per-head channels must be a positive multiple of 4");
-    if ((int64_t)heads * chead > MAX_DIM)
-        throw std::runtime_error(std::string(op) +
-                                 ": heads * channels above 1024");
-    const int epw = et == Elem::bf16 ? 2 : 1;
-    Plan p;
-    p.L.heads = heads;
-    p.L.wph = chead / epw;
-    p.L.logp = 0;
-    while ((1 << p.L.logp) < p.L.wph) ++p.L.logp;
-    p.L.words = heads * p.L.wph;
-    const int slots = heads << p.L.logp;
-    p.lanes = 2;
-    while (p.lanes < slots && p.lanes < 64) p.lanes <<= 1;
-    p.nch = 1;
-    while (p.lanes * p.nch < slots) p.nch <<= 1;
-    return p;
-}
-
 // W_e and, in the backward, the g_w accumulator live in one block's LDS as
 // fp32 [D][heads*chead] each: 2 * 4 * 8192 bytes = 64 KiB at this cap, what
 // a block gets without opting in to more.
@@ -666,7 +559,7 @@ void launch_gatv2_attn_fwd(hipStream_t s, Elem et, const void* xl,
                            const int64_t* src, const int64_t* dst_ptr,
                            int64_t n_dst, int heads, int chead, float slope,
                            void* out, float* lse) {
-    const Plan p = plan_for("gatv2_attn", et, heads, chead);
+    const Plan p = plan_for("gatv2_attn", et, heads, chead, MAX_DIM);
     launch_for(et, n_dst, [&](auto tag) {
         using T = typename decltype(tag)::type;
         QK_GATV2_DISPATCH(gatv2_attn_fwd_kernel, T, false, 2048, 0,
@@ -682,7 +575,7 @@ void launch_gatv2_attn_bwd(hipStream_t s, Elem et, const void* grad_out,
                            const int64_t* src, const int64_t* dst_ptr,
                            int64_t n_dst, int heads, int chead, float slope,
                            void* g_xl, void* g_xr, float* g_att) {
-    const Plan p = plan_for("gatv2_attn_backward", et, heads, chead);
+    const Plan p = plan_for("gatv2_attn_backward", et, heads, chead, MAX_DIM);
     if (!g_xl && !g_xr && !g_att) return;
     // one [heads*chead] fp32 accumulator in LDS (at most 4 KiB)
     const size_t lds = g_att ? (size_t)heads * chead * sizeof(float) : 0;
@@ -702,7 +595,7 @@ void launch_gatv2_attn_edge_fwd(hipStream_t s, Elem et, const void* xl,
                                 const int64_t* src, const int64_t* dst_ptr,
                                 int64_t n_dst, int heads, int chead,
                                 float slope, void* out, float* lse) {
-    const Plan p = plan_for("gatv2_attn_edge", et, heads, chead);
+    const Plan p = plan_for("gatv2_attn_edge", et, heads, chead, MAX_DIM);
     check_edge_plan("gatv2_attn_edge", p, edge_dim, heads, chead);
     const size_t lds = (size_t)edge_dim * heads * chead * sizeof(float);
     launch_for(et, n_dst, [&](auto tag) {
@@ -724,7 +617,8 @@ void launch_gatv2_attn_edge_bwd(hipStream_t s, Elem et, const void* grad_out,
                                 const int64_t* dst_ptr, int64_t n_dst,
                                 int heads, int chead, float slope, void* g_xl,
                                 void* g_xr, float* g_att, float* g_w) {
-    const Plan p = plan_for("gatv2_attn_edge_backward", et, heads, chead);
+    const Plan p = plan_for("gatv2_attn_edge_backward", et, heads, chead,
+                            MAX_DIM);
     check_edge_plan("gatv2_attn_edge_backward", p, edge_dim, heads, chead);
     if (!g_xl && !g_xr && !g_att && !g_w) return;
     // W_e, and the g_w accumulator behind it; g_att reuses the W_e area

@@ -2806,6 +2806,71 @@ gatv2_attn_edge_backward(
     return {g_xl, g_xr, g_att, g_w};
 }
 
+// Fused dot-product attention (transformer_kernels.hip): q one query row
+// per dst segment (more rows allowed), kv [n_src, 2 * heads*C] the key row
+// then the value row of each source node.  The operand checks shared by
+// the forward and the backward binding (the SegmentCall is built on q):
+struct TconvOperands {
+    torch::Tensor kv;
+    int chead;
+    TconvOperands(const SegmentCall& c, const torch::Tensor& kv_in,
+                  int64_t heads)
+        : chead(c.chead(heads)) {
+        TORCH_CHECK(chead % 4 == 0 && c.dim <= qk::kTconvMaxDim, c.op,
+                    ": needs per-head channels % 4 == 0 and heads * channels"
+                    " <= ", qk::kTconvMaxDim, ", got ", heads, " x ", chead);
+        TORCH_CHECK(c.feat.size(0) >= c.n_dst, c.op,
+                    ": q needs a row per dst_ptr segment");
+        TORCH_CHECK(kv_in.dim() == 2 && kv_in.size(1) == 2 * c.dim, c.op,
+                    ": kv must be [n_src, ", 2 * c.dim, "], got ",
+                    kv_in.sizes());
+        kv = c.arg("kv", kv_in, c.feat.scalar_type(), kv_in.sizes());
+    }
+};
+
+// (out [n_dst, heads*C], lse [n_dst, heads] fp32)
+std::tuple<torch::Tensor, torch::Tensor> tconv_attn(
+    torch::Tensor q, torch::Tensor kv, torch::Tensor src,
+    torch::Tensor dst_ptr, int64_t heads) {
+    SegmentCall c("tconv_attn", "q", q, false, &src, &dst_ptr);
+    TconvOperands o(c, kv, heads);
+    auto out = torch::empty({c.n_dst, c.dim}, c.feat.options());
+    auto lse = torch::empty({c.n_dst, heads},
+                            c.feat.options().dtype(torch::kFloat32));
+    qk::launch_tconv_attn_fwd(c.stream, c.elem, c.feat.data_ptr(),
+                              o.kv.data_ptr(), c.src_ptr(), c.dst_ptr_ptr(),
+                              c.n_dst, (int)heads, o.chead, out.data_ptr(),
+                              lse.data_ptr<float>());
+    return {out, lse};
+}
+
+// (g_q shaped like q with zero rows past n_dst, g_kv shaped like kv); an
+// output whose need_* flag is false is undefined.
+std::tuple<torch::Tensor, torch::Tensor> tconv_attn_backward(
+    torch::Tensor grad_out, torch::Tensor q, torch::Tensor kv,
+    torch::Tensor out, torch::Tensor lse, torch::Tensor src,
+    torch::Tensor dst_ptr, int64_t heads, bool need_gq, bool need_gkv) {
+    SegmentCall c("tconv_attn_backward", "q", q, false, &src, &dst_ptr);
+    TconvOperands o(c, kv, heads);
+    grad_out = c.arg("grad_out", grad_out, c.feat.scalar_type(),
+                     {c.n_dst, c.dim});
+    out = c.arg("out", out, c.feat.scalar_type(), {c.n_dst, c.dim});
+    lse = c.arg("lse", lse, torch::kFloat32, {c.n_dst, heads});
+    torch::Tensor g_q, g_kv;
+    if (need_gq) {
+        g_q = torch::empty_like(c.feat);
+        g_q.narrow(0, c.n_dst, c.feat.size(0) - c.n_dst).zero_();
+    }
+    if (need_gkv) g_kv = torch::zeros_like(o.kv);
+    qk::launch_tconv_attn_bwd(
+        c.stream, c.elem, grad_out.data_ptr(), c.feat.data_ptr(),
+        o.kv.data_ptr(), out.data_ptr(), lse.data_ptr<float>(), c.src_ptr(),
+        c.dst_ptr_ptr(), c.n_dst, (int)heads, o.chead,
+        need_gq ? g_q.data_ptr() : nullptr,
+        need_gkv ? g_kv.data_ptr() : nullptr);
+    return {g_q, g_kv};
+}
+
 void init_p2p(const std::vector<int>& devices) {
     // On an 8x MI355X node every pair is xGMI-connected: enable the full
     // clique (reference init_p2p, quiver_feature.cu:378-421; no NVLink-style
@@ -3112,6 +3177,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gatv2_attn_edge", &gatv2_attn_edge,
           "gatv2_attn with edge features projected inside the kernel");
     m.def("gatv2_attn_edge_backward", &gatv2_attn_edge_backward);
+    m.def("tconv_attn", &tconv_attn,
+          "fused scaled dot-product attention over dst-sorted edges: "
+          "(out, lse)");
+    m.def("tconv_attn_backward", &tconv_attn_backward);
+    m.def("tconv_max_dim", [] { return qk::kTconvMaxDim; },
+          "widest heads * channels the tconv_attn kernels serve");
     m.def("segment_softmax", &segment_softmax,
           "numerically-stable softmax over dst-sorted edge segments");
     m.def("segment_softmax_backward", &segment_softmax_backward);

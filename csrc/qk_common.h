@@ -18,6 +18,8 @@
 //                        mean, weighted segment sum, segment softmax, GAT
 //                        attention coefficients and dots
 //   gatv2_kernels.hip    fused GATv2 attention over dst-sorted edges
+//   transformer_kernels.hip  fused scaled dot-product attention
+//                        (TransformerConv) over dst-sorted edges
 //
 // Capability parity map (reference: quiver-team/torch-quiver):
 //   sample_kernels.hip  ~ srcs/cpp/include/quiver/cuda_random.cu.hpp +
@@ -544,5 +546,30 @@ void launch_gatv2_attn_edge_bwd(hipStream_t s, Elem et, const void* grad_out,
                                 const int64_t* dst_ptr, int64_t n_dst,
                                 int heads, int chead, float slope, void* g_xl,
                                 void* g_xr, float* g_att, float* g_w);
+
+// ---------- fused dot-product attention (transformer_kernels.hip) ---------
+//
+// q [>= n_dst, H*C] one query row per dst segment, kv [n_src, 2*H*C] the
+// key row followed by the value row of each source node, s = 1 / sqrt(C):
+//   logit[e,h] = s * <q[d,h,:], kv[src[e], h*C : (h+1)*C]>
+//   out[d,h,:] = sum_e softmax_seg(logit)[e,h] * kv[src[e], H*C + h*C ...]
+//   lse[d,h]   = log sum_e exp(logit[e,h])        (fp32, -inf when empty)
+// in one pass over each segment (online softmax, no per-edge tensor).
+// Throws unless C % 4 == 0 and H*C <= kTconvMaxDim, the widest row whose
+// kernels keep their state in registers without scratch.
+constexpr int kTconvMaxDim = 512;
+void launch_tconv_attn_fwd(hipStream_t s, Elem et, const void* q,
+                           const void* kv, const int64_t* src,
+                           const int64_t* dst_ptr, int64_t n_dst, int heads,
+                           int chead, void* out, float* lse);
+// Gradients of the above from the saved out and lse, one pass per segment.
+// A null g_q / g_kv skips that output; returns at once when both are.
+// g_kv [n_src, 2*H*C] is accumulated with atomics (pre-zeroed); g_q rows
+// [0, n_dst) are written directly.
+void launch_tconv_attn_bwd(hipStream_t s, Elem et, const void* grad_out,
+                           const void* q, const void* kv, const void* out,
+                           const float* lse, const int64_t* src,
+                           const int64_t* dst_ptr, int64_t n_dst, int heads,
+                           int chead, void* g_q, void* g_kv);
 
 }  // namespace qk

@@ -1,5 +1,6 @@
 // Element I/O and launch helpers shared by the message-passing kernel
-// files (segment_kernels.hip, gatv2_kernels.hip).  Internal to csrc/:
+// files (segment_kernels.hip, gatv2_kernels.hip, transformer_kernels.hip).
+// Internal to csrc/:
 // device code only, included by .hip translation units.
 #pragma once
 #include <hip/hip_bf16.h>

@@ -7,8 +7,9 @@ bench.py live here.  The layers follow PyG's bipartite convention: forward
 edge_index[1] indexing x_dst — exactly what GraphSageSampler's adjs feed.
 On GPU tensors with dst-sorted edges (the sampler's layout) aggregation and
 attention run on the fused HIP segment kernels (csrc/segment_kernels.hip,
-csrc/gatv2_kernels.hip) through the autograd functions below; other inputs take the plain torch
-index_add / scatter_reduce chain.
+csrc/gatv2_kernels.hip, csrc/transformer_kernels.hip) through the autograd
+functions below; other inputs take the plain torch index_add /
+scatter_reduce chain.
 """
 import functools
 from typing import Tuple
@@ -23,8 +24,8 @@ from . import _ext
 # not clone()/.to()/indexing)
 from .pyg.sage_sampler import DST_PTR_ATTR
 
-__all__ = ["SAGEConv", "GATConv", "GATv2Conv", "GraphSAGE", "GAT",
-           "QLinear"]
+__all__ = ["SAGEConv", "GATConv", "GATv2Conv", "TransformerConv",
+           "GraphSAGE", "GAT", "GraphTransformer", "QLinear"]
 
 
 def _as_pair(x):
@@ -212,6 +213,33 @@ class _GatV2AttnEdge(torch.autograd.Function):
                 None, None, None, None)
 
 
+class _TConvAttn(torch.autograd.Function):
+    """Fused scaled dot-product attention over dst-sorted edges
+    (csrc/transformer_kernels.hip): q [>= n_dst, H*C] one query row per dst,
+    kv [n_src, 2*H*C] the key row then the value row of each source,
+    out[d,h,:] = sum_e softmax_seg(<q[d,h], k[src_e,h]> / sqrt(C)) *
+    v[src_e,h,:].  One pass over each segment in either direction (online
+    softmax forward, alpha recomputed from the saved log-sum-exp backward)
+    and no [E,H,C] tensor at all."""
+
+    @staticmethod
+    def forward(ctx, q, kv, src, dst_ptr, heads):
+        out, lse = _ext.tconv_attn(q, kv, src, dst_ptr, heads)
+        ctx.save_for_backward(q, kv, out, lse, src, dst_ptr)
+        ctx.heads = heads
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        q, kv, out, lse, src, dst_ptr = ctx.saved_tensors
+        need = ctx.needs_input_grad[:2]
+        g_q, g_kv = _ext.tconv_attn_backward(
+            grad_out.contiguous(), q, kv, out, lse, src, dst_ptr, ctx.heads,
+            *need)
+        return (g_q if need[0] else None, g_kv if need[1] else None,
+                None, None, None)
+
+
 class _QLinearFn(torch.autograd.Function):
     """Linear layer whose weight gradient uses the split-K HIP kernel
     (csrc/wgrad_kernels.hip).
@@ -256,15 +284,20 @@ class _QLinearFn(torch.autograd.Function):
 _WGRAD_MIN_K = 16384
 
 
+def _qlinear(x, weight, bias):
+    """F.linear with QLinear's routing."""
+    if (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
+            and x.size(0) >= _WGRAD_MIN_K and torch.is_grad_enabled()):
+        return _QLinearFn.apply(x, weight, bias)
+    return F.linear(x, weight, bias)
+
+
 class QLinear(nn.Linear):
     """nn.Linear with the custom tall-skinny weight-grad path on GPU fp32
     inputs with a large leading (frontier) dimension."""
 
     def forward(self, x):
-        if (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
-                and x.size(0) >= _WGRAD_MIN_K and torch.is_grad_enabled()):
-            return _QLinearFn.apply(x, self.weight, self.bias)
-        return F.linear(x, self.weight, self.bias)
+        return _qlinear(x, self.weight, self.bias)
 
 
 _ARANGE_CACHE = {}
@@ -686,6 +719,109 @@ class GATv2Conv(nn.Module):
         return out
 
 
+class TransformerConv(nn.Module):
+    """Graph transformer convolution (Shi et al., "Masked Label Prediction:
+    Unified Message Passing Model for Semi-Supervised Classification"),
+    PyG's parameter names and semantics without edge features: the logit of
+    an edge is <lin_query(x_dst)[dst], lin_key(x_src)[src]> / sqrt(C) per
+    head, softmax over the incoming edges of each dst, and the message is
+    lin_value(x_src)[src].  root_weight adds lin_skip(x_dst); beta gates the
+    two with sigmoid(lin_beta([out, x_r, out - x_r])).
+
+    Keys and values come from one GEMM over x_src (the lin_key and lin_value
+    weights concatenated), so a source node owns one [2 * heads * C] row.
+    With sorted_dst=True (GraphSageSampler's adjs) on GPU tensors of fp32
+    or bf16, out_channels % 4 == 0 and heads * out_channels within the
+    kernels' cap (_ext.tconv_max_dim()), the attention and aggregation run
+    in the fused kernels of csrc/transformer_kernels.hip.  Attention dropout
+    in training mode, and any other input, takes the plain torch chain
+    below."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True,
+                 beta=False, dropout=0.0, bias=True, root_weight=True,
+                 sorted_dst=False):
+        super().__init__()
+        in_src, in_dst = _as_pair(in_channels)
+        self.sorted_dst = sorted_dst
+        self.heads = heads
+        self.out_channels = out_channels
+        self.concat = concat
+        self.beta = beta
+        self.dropout = dropout
+        self.root_weight = root_weight
+        self.lin_key = QLinear(in_src, heads * out_channels)
+        self.lin_query = QLinear(in_dst, heads * out_channels)
+        self.lin_value = QLinear(in_src, heads * out_channels)
+        out_dim = heads * out_channels if concat else out_channels
+        self.lin_skip = QLinear(in_dst, out_dim, bias=bias)
+        # as in PyG, lin_skip (and lin_beta with beta) exist whatever
+        # root_weight says and are unused without it
+        self.lin_beta = QLinear(3 * out_dim, 1, bias=False) if beta else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for lin in (self.lin_key, self.lin_query, self.lin_value,
+                    self.lin_skip, self.lin_beta):
+            if lin is not None:
+                lin.reset_parameters()
+
+    def _fused_ok(self, q, dst):
+        H, C = self.heads, self.out_channels
+        return (self.sorted_dst and q.is_cuda and dst.numel() > 0
+                and q.dtype in (torch.float32, torch.bfloat16)
+                and C % 4 == 0 and H * C <= _ext.tconv_max_dim()
+                and not (self.training and self.dropout > 0))
+
+    def forward(self, x, edge_index, size: Tuple[int, int] = None):
+        x_src, x_dst = _as_pair(x)
+        src, dst = edge_index[0], edge_index[1]
+        H, C = self.heads, self.out_channels
+        n_dst = x_dst.size(0) if size is None else int(size[1])
+
+        q = self.lin_query(x_dst)
+        # keys and values in one pass over x_src, the largest matrix of a
+        # step: row i is [lin_key(x_src)[i], lin_value(x_src)[i]]
+        kv = _qlinear(
+            x_src, torch.cat([self.lin_key.weight, self.lin_value.weight]),
+            torch.cat([self.lin_key.bias, self.lin_value.bias]))
+
+        if self._fused_ok(q, dst):
+            out = _TConvAttn.apply(q, kv, src,
+                                   _dst_ptr_for(edge_index, n_dst), H)
+            out = out if self.concat else out.view(n_dst, H, C).mean(1)
+        else:
+            k3 = kv[:, :H * C].view(-1, H, C)
+            v3 = kv[:, H * C:].view(-1, H, C)
+            alpha = (q.view(-1, H, C)[dst] * k3[src]).sum(-1) / C ** 0.5
+            # segment softmax over the incoming edges of each dst
+            amax = torch.full((n_dst, H), float("-inf"), dtype=alpha.dtype,
+                              device=alpha.device)
+            amax = amax.scatter_reduce(
+                0, dst.unsqueeze(-1).expand_as(alpha), alpha, reduce="amax",
+                include_self=True)
+            alpha = (alpha - amax[dst]).exp()
+            denom = torch.zeros((n_dst, H), dtype=alpha.dtype,
+                                device=alpha.device)
+            denom.index_add_(0, dst, alpha)
+            alpha = alpha / denom[dst].clamp(min=1e-16)
+            if self.training and self.dropout > 0:
+                alpha = F.dropout(alpha, p=self.dropout)
+            out = torch.zeros((n_dst, H, C), dtype=kv.dtype,
+                              device=kv.device)
+            out.index_add_(0, dst, v3[src] * alpha.unsqueeze(-1))
+            out = (out.reshape(n_dst, H * C) if self.concat
+                   else out.mean(1))
+        if self.root_weight:
+            x_r = self.lin_skip(x_dst)
+            if self.lin_beta is not None:
+                b = torch.sigmoid(
+                    self.lin_beta(torch.cat([out, x_r, out - x_r], dim=-1)))
+                out = b * x_r + (1 - b) * out
+            else:
+                out = out + x_r
+        return out
+
+
 class GraphSAGE(nn.Module):
     """Multi-layer GraphSAGE matching the reference examples' training/
     inference loop (forward(x, adjs) over per-hop bipartite graphs)."""
@@ -776,6 +912,42 @@ class GAT(nn.Module):
                                   edge_attr=edge_attr, edge_id=e_id)
             if i != self.num_layers - 1:
                 x = F.elu(x, inplace=True)
+                if self.dropout > 0:
+                    x = F.dropout(x, p=self.dropout, training=self.training)
+        return torch.log_softmax(x, dim=-1)
+
+
+class GraphTransformer(nn.Module):
+    """Multi-layer TransformerConv model (the UniMP stack without label
+    propagation), shaped like GAT: hidden layers concatenate `heads` heads,
+    the output layer has one."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels,
+                 num_layers=2, heads=4, dropout=0.5, beta=True,
+                 sorted_dst=True):
+        super().__init__()
+        self.num_layers = num_layers
+        self.dropout = dropout
+        self.convs = nn.ModuleList()
+        conv = functools.partial(TransformerConv, beta=beta,
+                                 sorted_dst=sorted_dst)
+        # sorted_dst: GraphSageSampler emits dst-sorted adjs -> fused kernel
+        if num_layers == 1:
+            self.convs.append(conv(in_channels, out_channels, heads=1))
+        else:
+            self.convs.append(conv(in_channels, hidden_channels, heads=heads))
+            for _ in range(num_layers - 2):
+                self.convs.append(conv(hidden_channels * heads,
+                                       hidden_channels, heads=heads))
+            self.convs.append(conv(hidden_channels * heads, out_channels,
+                                   heads=1))
+
+    def forward(self, x, adjs):
+        for i, (edge_index, _, size) in enumerate(adjs):
+            x_target = x[:size[1]]
+            x = self.convs[i]((x, x_target), edge_index, size)
+            if i != self.num_layers - 1:
+                x = F.relu(x, inplace=True)
                 if self.dropout > 0:
                     x = F.dropout(x, p=self.dropout, training=self.training)
         return torch.log_softmax(x, dim=-1)
